@@ -14,6 +14,12 @@ scaling: one view per GPU per step).  value = views/s of full train steps over t
 
 Contract: python bench.py --gpus N --steps K --warmup W  ->  ONE JSON line on rank 0.
 
+A plain run does what the headline needs and nothing else: set-up, warm-up, the K timed steps, the outputs of the last step
+(--dump-outputs DIR) and the line (metric, value, unit, n_gpus, steps, warmup, ms_per_step, higher_is_better, scaling, vs_baseline,
+dtype, data, config).  --full adds every secondary measurement to the same line: the roofline (hipEvent brackets of the composite
+forward inside the timed region), the per-kernel table, the step without the depth-key promise, eval renders, measured device
+peaks, the CPU baseline, the dense variant and the step with the weights model inside (the --no-* switches drop single legs of it).
+
 Launch forms.  Under a launcher (`python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`: WORLD_SIZE is set)
 this process is one of the N ranks.  As plain `python bench.py --gpus N` with N > 1 (WORLD_SIZE unset) it STARTS the N ranks
 itself -- it re-executes under `torch.distributed.run` on 127.0.0.1 with a free port and relays rank 0's line -- and it fails
@@ -335,6 +341,45 @@ def dense_variant(args, device, steps=20):
     return out
 
 
+DUMP_ROWS = 32768              # per-Gaussian arrays: this many rows, the same seeded choice in every run
+DUMP_BUDGET = 60_000_000       # bytes over all files of --dump-outputs
+
+
+def dump_outputs(dirname, out, train):
+    """--dump-outputs: what the last timed step handed its caller, one DIR/<name>.npy per array -- the loss (train steps) and every tensor of
+    the render()-shaped dict (`viewspace_points` as its gradient).  Floating arrays as float32, integer and boolean ones as float64 (exact).
+    Per-Gaussian arrays hold the rows of a fixed seeded sample (DUMP_ROWS of them); should the files still exceed DUMP_BUDGET, the largest
+    array is cut to a seeded half of its entries until they fit.  Called before anything else runs on the device: the fused step's buffers
+    belong to the next step.  That step started from the set-up's parameters (main() puts them back in front of it), so the same arguments
+    give the same arrays in every run, up to the summation order of the backward's float atomics.  The parameters it updated are not
+    written: their Adam moments carry the whole trajectory, which those atomics make differ from run to run (Adam's eps = 1e-15 turns
+    near-zero gradients into full steps)."""
+    loss, pkg = (out if train else (None, out))
+    n = int(pkg["radii"].shape[0])
+    rows = torch.from_numpy(np.sort(np.random.default_rng(0).choice(n, min(n, DUMP_ROWS), replace=False)))
+    named = [("loss", loss)] if loss is not None else []
+    for k, v in pkg.items():
+        if k == "viewspace_points" and isinstance(v, torch.Tensor):
+            k, v = "viewspace_points_grad", v.grad
+        if isinstance(v, torch.Tensor):
+            named.append((k, v))
+    arrs = {}
+    with torch.no_grad():
+        for k, v in named:
+            v = v.detach()
+            if v.dim() > 0 and v.shape[0] == n and n > len(rows):
+                v = v[rows.to(v.device)]
+            v = v.cpu()
+            arrs[k] = v.numpy().astype(np.float32 if v.is_floating_point() else np.float64)
+    while sum(a.nbytes for a in arrs.values()) > DUMP_BUDGET:
+        k = max(arrs, key=lambda name: arrs[name].nbytes)
+        a = arrs[k].reshape(-1)
+        arrs[k] = a[np.sort(np.random.default_rng(1).choice(a.size, a.size // 2, replace=False))]
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
+
+
 def kernel_source_stamp():
     """Identifies the composite kernels' source: a traffic figure from a PMC run is only quoted for the kernel it measured."""
     return _sha16(os.path.join(ROOT, "gaussianprediction_amd", "csrc", "raster_kernels.hip"))
@@ -386,9 +431,16 @@ def main():
                          "config.exposed_wait_ms_per_step (adds a few stream bubbles: an A/B aid, not the headline run)")
     ap.add_argument("--dry-launch", action="store_true",
                     help="launch path only: N ranks rendezvous over gloo, one all-reduce, one JSON line, no device work")
+    ap.add_argument("--full", action="store_true",
+                    help="every secondary measurement beside the headline (roofline, per-kernel table, depth-promise leg, eval renders, device "
+                         "peaks, CPU baseline, dense variant, weights-model step); off: set-up, warm-up, the timed steps and the line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0; see dump_outputs)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args, sys.argv[1:])             # does not return
     if args.dry_launch:
@@ -417,6 +469,12 @@ def main():
                    sharded=False if (args.replicated_adam or args.factorised_sh) else None, chain_sh=not args.no_chain_sh, fused=not args.no_fused,
                    factorised_sh=args.factorised_sh)
     ts.early_adam = not args.no_early_adam
+    # --dump-outputs: the last timed step starts from the parameters as the set-up left them (seeded: the same in every run), so that what
+    # it returns is the same in every run -- the steps before it train as ever, and the float atomics of their backward make the
+    # trajectory differ from run to run (dump_outputs)
+    setup_params = None
+    if args.dump_outputs:
+        setup_params = [(p, p.detach().clone()) for g in pc.optimizer.param_groups for p in g["params"]]
 
     def one_step(i):
         view = i * world + rank            # rank r renders view world*i + r
@@ -439,7 +497,7 @@ def main():
     for i in range(args.warmup):
         one_step(preroll + i)
     torch.cuda.synchronize()
-    if rank == 0:
+    if rank == 0 and args.full:
         from gaussianprediction_amd.rasterizer import raster_forward_debug as _rfd
         from gaussianprediction_amd.renderer import _settings as _st
         with torch.no_grad():
@@ -449,29 +507,107 @@ def main():
         torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
-    # timed region: only the roofline kernel (composite forward) is bracketed by hipEvents -- every
+    # timed region: only the roofline kernel (composite forward) is bracketed by hipEvents, and only with --full -- every
     # bracket costs ~10 us of stream bubble, so the full per-kernel table is taken in a separate pass
-    _lib.check(_lib.lib().gp_debug_option(12, int(args.roofline_sample_period)), "gp_debug_option")
-    _lib.profile_enable(1)
-    _lib.profile_collect()
+    if args.full:
+        _lib.check(_lib.lib().gp_debug_option(12, int(args.roofline_sample_period)), "gp_debug_option")
+        _lib.profile_enable(1)
+        _lib.profile_collect()
     if args.time_waits and getattr(ts.reducer, "exposed_wait_ms", None):
         ts.reducer.time_waits = True
         ts.reducer.exposed_wait_ms(1)                  # (drop what the warm-up recorded)
     torch.cuda.synchronize()
     with no_gc():
         t0 = time.perf_counter()
-        pkg = None
+        paused = 0.0
         for i in range(args.steps):
+            if setup_params is not None and i == args.steps - 1:
+                ts.sync_params()
+                torch.cuda.synchronize()
+                tp = time.perf_counter()                # (the clock stops while the set-up's parameters are put back)
+                with torch.no_grad():
+                    for p, p0 in setup_params:
+                        p.copy_(p0)
+                torch.cuda.synchronize()
+                paused = time.perf_counter() - tp
             out = one_step(preroll + args.warmup + i)
-            pkg = out if args.render_only else out[1]
-        ts.sync_params()                            # (N > 1: the last step's parameter all-gather belongs to the timed work)
+        ts.sync_params()                           # (N > 1: the last step's parameter all-gather belongs to the timed work)
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
-        elapsed = time.perf_counter() - t0
+        elapsed = time.perf_counter() - t0 - paused
     waits = ts.reducer.exposed_wait_ms(args.steps) if (args.time_waits and getattr(ts.reducer, "exposed_wait_ms", None)) else None
     if waits is not None:
         ts.reducer.time_waits = False
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, train=not args.render_only)
+    if args.full:
+        full = full_measurements(args, rank, world, pc, cams, ts, one_step, preroll)
+    if world > 1:
+        tmax = torch.tensor([elapsed], device=device, dtype=torch.float64)
+        dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
+        elapsed = float(tmax.item())
+
+    if rank == 0:
+        ms_per_step = 1000.0 * elapsed / args.steps
+        views_per_s = world * args.steps / elapsed
+        W, H = args.width, args.height
+        result = {
+            "metric": f"rendered views/s ({'eval render' if args.render_only else 'full train step'}) "
+                      f"@{args.gaussians / 1e6:g}M Gaussians {args.width}x{args.height}",
+            "value": round(views_per_s, 3), "unit": "views/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f32", "data": "synthetic",
+            "config": {"workload": "configs[2]: HyperNeRF-like 1M Gaussians, 1352x1014, stage-3 full train step "
+                                   "(deform, raster, L1+SSIM loss, Adam: all HIP kernels)"
+                       if not args.render_only else "configs[2] eval render (forward only)",
+                       "gaussians": args.gaussians, "width": W, "height": H, "keypoints": args.keypoints,
+                       "nearest_num": args.nearest_num, "time_freq": args.time_freq, "iteration": args.iteration,
+                       "parallelism": f"view-parallel x{world}",
+                       "ranks_seen_by_rccl": dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1,
+                       "self_launched": os.environ.get("GP_BENCH_SELF_LAUNCHED") == "1",
+                       "gradient_exchange": None if not ts.reducer.enabled else (
+                           ("all-reduce(SUM) of the flat gradient bucket + replicated Adam" if not getattr(ts, "factorised_sh", False) else
+                            "replicated Adam; SH gradients as (dL/dRGB, view direction) factors: one all-gather of 24 B per Gaussian and rank, summed "
+                            "over the views in rank order on every rank (gp_sh_factor_gradient); all-reduce(SUM) of everything else") if not ts.sharded else
+                           "reduce-scatter(SUM) per region -> Adam on 1/N of every region -> asynchronous all-gather of the parameters"
+                           + ("; SH regions: Adam + all-gather on a side stream from the moment their reduce-scatter lands, awaited by the "
+                              "next forward in front of its SH->RGB kernel only" if getattr(ts, "chain_sh", False) else "")
+                           + (" [ONE-rank group, GP_DIST_FORCE_SINGLE: the code path, not a scaling number]" if world == 1 else "")),
+                       "xgmi_bytes_sent_per_rank_per_step": None if world == 1 else (
+                           getattr(ts.reducer, "bytes_sent_per_step", None) or
+                           (int(2 * 4 * ts.bucket.flat.numel() * (world - 1) / world) if not getattr(ts, "factorised_sh", False) else
+                            # the all-reduce of everything but the SH tensors + the factor all-gather (every rank sends its 24 B per Gaussian to world - 1 peers)
+                            int(2 * 4 * (ts.bucket.flat.numel() - pc._features_dc.numel() - pc._features_rest.numel()) * (world - 1) / world)
+                            + 24 * int(pc._features_dc.shape[0]) * (world - 1))),
+                       "exposed_wait_ms_per_step": waits,          # (--time-waits: compute-stream time inside waits for collectives, rank 0)
+                       "step_driver": (f"one library call per step (gp_train_step_run): {getattr(ts, 'fused_steps', 0)} of the steps since the set-up"
+                                       + ("; the per-Gaussian tensors' Adam update rides in the launch of the keypoint MLP's data backward "
+                                          "(kernels_ms.adam = that launch + the MLP tensors' update; no mlp_bwd_data entry)"
+                                          if (getattr(getattr(getattr(ts, "_fused_plan", None), "upd", None), "adam_early_mask", 0) and world == 1) else "")
+                                       if getattr(ts, "fused_steps", 0) else "autograd graph (render -> loss -> backward -> FusedAdam.step)"),
+                       "binning": "exact (R read back every step)" if args.exact_binning else
+                                  f"capacity mode in warm-up and timed steps (no host sync; {preroll} exact-mode set-up steps before the "
+                                  f"warm-up; {getattr(ts, 'redone', 0)} frames repeated after overflow)",
+                       "depth_sort": "32-bit keys, four 8-bit passes" if not getattr(ts, "last_depth_key_promise", None) else
+                                     (f"{ts.last_depth_key_promise[0]}-bit keys above a promised base ({-(-ts.last_depth_key_promise[0] // 8)} passes; the "
+                                      "projection kernel checks the promise, a broken one repeats the frame like a binning overflow; visible depths "
+                                      f"seen in the set-up steps: {_key_depth(ts._key_lo):.3f} .. {_key_depth(ts._key_hi):.3f})"),
+                       "keypoint_weights": "raw_weights / knn_idx are inputs of the step (BASELINE.json north_star); the reference "
+                                           "recomputes them per frame (hash-grid weights model + kNN): see train_step_with_weights_model_ms"},
+        }
+        if args.full:
+            full_result(args, device, world, pc, cams, gts, margs, ts, preroll, result, full)
+        print(json.dumps(result), flush=True)
+    if world > 1:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def full_measurements(args, rank, world, pc, cams, ts, one_step, preroll):
+    """--full, every rank, right behind the timed region: the roofline kernel's brackets, the step without the depth-key promise, eval
+    renders and the untimed per-kernel pass."""
+    from gaussianprediction_amd import _lib
     prof = _lib.profile_collect()
     _lib.profile_enable(0)
     _lib.check(_lib.lib().gp_debug_option(12, 0), "gp_debug_option")
@@ -557,235 +693,193 @@ def main():
     torch.cuda.synchronize()
     prof_all = _lib.profile_collect()
     _lib.profile_enable(0)
-    if world > 1:
-        tmax = torch.tensor([elapsed], device=device, dtype=torch.float64)
-        dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
-        elapsed = float(tmax.item())
+    return SimpleNamespace(prof=prof, prof_all=prof_all, no_promise_ms=no_promise_ms, four_pass_sort_ms=four_pass_sort_ms, eval_ms=eval_ms,
+                           eval_fps=eval_fps, eval_fps_exact=eval_fps_exact if eval_fps is not None else None,
+                           eval_again=eval_again if eval_fps is not None else None)
 
-    if rank == 0:
-        ms_per_step = 1000.0 * elapsed / args.steps
-        views_per_s = world * args.steps / elapsed
-        # algorithmic bytes of the composite forward pass: 44 R + 8 T + 28 P
-        W, H = args.width, args.height
-        T = ((W + 15) // 16) * ((H + 15) // 16)
-        P = W * H
-        # R of the last rendered view (re-render to read it)
-        from gaussianprediction_amd.rasterizer import raster_forward_debug
-        from gaussianprediction_amd.renderer import _settings
-        with torch.no_grad():
-            cam = cams[((preroll + args.warmup + args.steps - 1) * world) % len(cams)]
-            t = torch.from_numpy(cam.time).float().to(device)
-            xyz, q, s, o = pc(t, args.iteration)
-            dbg = raster_forward_debug(_settings(cam, pc, ts.bg, 1.0), xyz, o, shs=pc.get_features, scales=s, rotations=q)
-        R, n_vis = dbg["R"], int((dbg["radii"] > 0).sum())
-        R0 = getattr(main, "_R0", None)
-        nprof = min(args.steps, 5)
-        kern = {k: {"launches_per_step": round(v[0] / nprof, 2), "ms_per_step": round(v[1] / nprof, 4)} for k, v in sorted(prof_all.items())}
-        roof = None
-        if "composite_fwd" in prof:
-            avg_ms = prof["composite_fwd"][1] / prof["composite_fwd"][0]
-            bytes_alg = 44 * R + 8 * T + 28 * P
-            ach = bytes_alg / (avg_ms * 1e-3) / 1e9
-            roof = {"kernel": "composite_fwd", "bound": "hbm", "achieved": round(ach, 1), "peak": HBM_PEAK_GBS,
-                    "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": None,
-                    "algorithmic_bytes": bytes_alg, "avg_ms": round(avg_ms, 4),
-                    # hipEvent pairs around the kernel's launches INSIDE the timed region: every `event_sample_period`-th step
-                    "event_samples": int(prof["composite_fwd"][0]), "event_sample_period": int(args.roofline_sample_period),
-                    # `bound` is the contract's roofline (SURVEY 8d prices the kernel in bytes); what the kernel WAITS for is the vector ALU
-                    # (valu_issue_frac / valu_busy below): the fraction of the HBM roof is therefore capped by instructions, not by traffic
-                    "binding_resource": "valu"}
-            # HBM bytes per launch from the PMC passes (tools/pmc_hbm.py): quoted only while the file describes THIS kernel
-            # source (it is stamped with the source's hash); otherwise null -- a stale constant is not a measurement
-            tf = os.path.join(ROOT, "profiles", "composite_fwd_traffic.json")
-            roof["traffic_source"] = None
-            roof["traffic_measured_in_this_run"] = False          # (`traffic` is a stored PMC result of the same kernel source)
+
+def full_result(args, device, world, pc, cams, gts, margs, ts, preroll, result, full):
+    """--full, rank 0: the secondary fields of the line, from what full_measurements() collected and from runs of their own (device
+    peaks, CPU baseline, dense variant, weights-model step)."""
+    from gaussianprediction_amd import _lib
+    from gaussianprediction_amd.train_step import TrainStep
+    prof, prof_all = full.prof, full.prof_all
+    # algorithmic bytes of the composite forward pass (BASELINE.md section 4): 44 R + 8 T + 28 P
+    W, H = args.width, args.height
+    T = ((W + 15) // 16) * ((H + 15) // 16)
+    P = W * H
+    # R of the last rendered view (re-render to read it)
+    from gaussianprediction_amd.rasterizer import raster_forward_debug
+    from gaussianprediction_amd.renderer import _settings
+    with torch.no_grad():
+        cam = cams[((preroll + args.warmup + args.steps - 1) * world) % len(cams)]
+        t = torch.from_numpy(cam.time).float().to(device)
+        xyz, q, s, o = pc(t, args.iteration)
+        dbg = raster_forward_debug(_settings(cam, pc, ts.bg, 1.0), xyz, o, shs=pc.get_features, scales=s, rotations=q)
+    R, n_vis = dbg["R"], int((dbg["radii"] > 0).sum())
+    R0 = getattr(main, "_R0", None)
+    nprof = min(args.steps, 5)
+    kern = {k: {"launches_per_step": round(v[0] / nprof, 2), "ms_per_step": round(v[1] / nprof, 4)} for k, v in sorted(prof_all.items())}
+    roof = None
+    if "composite_fwd" in prof:
+        avg_ms = prof["composite_fwd"][1] / prof["composite_fwd"][0]
+        bytes_alg = 44 * R + 8 * T + 28 * P
+        ach = bytes_alg / (avg_ms * 1e-3) / 1e9
+        roof = {"kernel": "composite_fwd", "bound": "hbm", "achieved": round(ach, 1), "peak": HBM_PEAK_GBS,
+                "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": None,
+                "algorithmic_bytes": bytes_alg, "avg_ms": round(avg_ms, 4),
+                # hipEvent pairs around the kernel's launches INSIDE the timed region: every `event_sample_period`-th step
+                "event_samples": int(prof["composite_fwd"][0]), "event_sample_period": int(args.roofline_sample_period),
+                # `bound` is the contract's roofline (SURVEY 8d prices the kernel in bytes); what the kernel WAITS for is the vector ALU
+                # (valu_issue_frac / valu_busy below): the fraction of the HBM roof is therefore capped by instructions, not by traffic
+                "binding_resource": "valu"}
+        # HBM bytes per launch from the PMC passes (tools/pmc_hbm.py): quoted only while the file describes THIS kernel
+        # source (it is stamped with the source's hash); otherwise null -- a stale constant is not a measurement
+        tf = os.path.join(ROOT, "profiles", "composite_fwd_traffic.json")
+        roof["traffic_source"] = None
+        roof["traffic_measured_in_this_run"] = False          # (`traffic` is a stored PMC result of the same kernel source)
+        try:
+            # contributing (pixel, splat) pairs, counted by the kernel's counting variant on one untimed render of the last view,
+            # and the instruction floor they imply: every contributing pair costs at least the straight-line visit of the
+            # kernel (19 vector-ALU instructions per 64 pairs: the visit of a fast block, raster_kernels.hip CF2_VISIT), on 1024 SIMDs issuing
+            # one wave64 instruction per 4 cycles
+            import ctypes as C
+            L = _lib.lib()
+            _lib.check(L.gp_debug_option(0, 3), "opt")
+            cnt = (C.c_uint64 * 4)()
+            _lib.check(L.gp_debug_counters(cnt), "counters")          # (clears what earlier renders left)
+            with torch.no_grad():
+                raster_forward_debug(_settings(cam, pc, ts.bg, 1.0), xyz, o, shs=pc.get_features, scales=s, rotations=q)
+            _lib.check(L.gp_debug_counters(cnt), "counters")
+            _lib.check(L.gp_debug_option(0, 0), "opt")
+            MIN_VALU = 19
+            roof["contributing_pairs"], roof["evaluated_pairs"] = int(cnt[0]), int(cnt[1])
+            roof["min_valu_per_pair"] = MIN_VALU
+            roof["valu_lower_bound_ms"] = round(int(cnt[0]) * MIN_VALU / 64.0 * 4.0 / 1024.0 / (SHADER_CLOCK_GHZ * 1e9) * 1e3, 4)
+        except Exception as e:
+            roof["contributing_pairs"] = f"failed: {e}"
             try:
-                # contributing (pixel, splat) pairs, counted by the kernel's counting variant on one untimed render of the last view,
-                # and the instruction floor they imply: every contributing pair costs at least the straight-line visit of the
-                # kernel (19 vector-ALU instructions per 64 pairs: the visit of a fast block, raster_kernels.hip CF2_VISIT), on 1024 SIMDs issuing
-                # one wave64 instruction per 4 cycles
-                import ctypes as C
-                L = _lib.lib()
-                _lib.check(L.gp_debug_option(0, 3), "opt")
-                cnt = (C.c_uint64 * 4)()
-                _lib.check(L.gp_debug_counters(cnt), "counters")          # (clears what earlier renders left)
-                with torch.no_grad():
-                    raster_forward_debug(_settings(cam, pc, ts.bg, 1.0), xyz, o, shs=pc.get_features, scales=s, rotations=q)
-                _lib.check(L.gp_debug_counters(cnt), "counters")
-                _lib.check(L.gp_debug_option(0, 0), "opt")
-                MIN_VALU = 19
-                roof["contributing_pairs"], roof["evaluated_pairs"] = int(cnt[0]), int(cnt[1])
-                roof["min_valu_per_pair"] = MIN_VALU
-                roof["valu_lower_bound_ms"] = round(int(cnt[0]) * MIN_VALU / 64.0 * 4.0 / 1024.0 / (SHADER_CLOCK_GHZ * 1e9) * 1e3, 4)
-            except Exception as e:
-                roof["contributing_pairs"] = f"failed: {e}"
-                try:
-                    _lib.check(_lib.lib().gp_debug_option(0, 0), "opt")
-                except Exception:
-                    pass
-            if os.path.exists(tf):
-                try:
-                    tj = json.load(open(tf))
-                    if tj.get("kernel_source_sha16") == kernel_source_stamp():
-                        roof["traffic"] = tj.get("hbm_bytes_per_launch")
-                        # (the same counters read as if every request were a 128-byte one: what the traffic could be at most if the
-                        # gather calibration of the PMC file's header did not hold)
-                        roof["traffic_upper_bound"] = tj.get("hbm_bytes_per_launch_upper_bound")
-                        roof["traffic_source"] = tj.get("source")
-                        vj = tj.get("valu")
-                        if vj:
-                            # the kernel is declared "hbm"-bound by the contract's formula, but what it waits for is the vector
-                            # ALU: the instruction floor (every SIMD issuing one wave64 VALU instruction per 4 cycles) and how busy
-                            # the VALUs were, from the SQ counters of the same kernel source
-                            cycles = avg_ms * 1e-3 * SHADER_CLOCK_GHZ * 1e9
-                            roof["valu_floor_ms"] = round(4.0 * vj["SQ_INSTS_VALU"] / 1024.0 / (SHADER_CLOCK_GHZ * 1e9) * 1e3, 4)
-                            roof["valu_issue_frac"] = round(roof["valu_floor_ms"] / avg_ms, 4)     # the roof the kernel actually runs under
-                            roof["valu_busy"] = round(min(1.0, 4.0 * vj["SQ_ACTIVE_INST_VALU"] / (1024.0 * cycles)), 3)
-                            roof["valu_insts_per_launch"] = int(vj["SQ_INSTS_VALU"])
-                            roof["valu_source"] = vj.get("source")
-                    else:
-                        roof["traffic_source"] = "profiles/composite_fwd_traffic.json describes another kernel source: not quoted"
-                except Exception:
-                    pass
-        # the other HBM-bound kernels of the step against the same roofline (algorithmic bytes: SURVEY.md 8d / DESIGN.md 4;
-        # durations from the untimed per-kernel pass), reported beside the contract's `roofline` object
-        others = {}
-        N = args.gaussians
-        # Adam: 28 B per parameter the launch ACTUALLY updates (p, g, m, v read; p, m, v written).  In single-view single-rank
-        # steps the two SH tensors (48 of the 59 floats per Gaussian) are updated inside the rasterizer backward instead
-        # (gp_adam_fuse) and their bytes belong to preprocess_bwd's line.
-        sh_fused = bool(getattr(ts, "fuse_sh_adam", False) and not ts.reducer.enabled and ts.batch == 1)
-        sh_ids = {id(pc._features_dc), id(pc._features_rest)}
-        n_adam = sum(int(p.numel()) for p in ts.bucket.params if not (sh_fused and id(p) in sh_ids))
-        n_sh = sum(int(p.numel()) for p in ts.bucket.params if id(p) in sh_ids)
-        # preprocess backward per Gaussian: reads means 12 + scales 12 + rotations 16 + SH 192 + radii 4 + clamp flags 1 + the
-        # 40 useful bytes of its accumulator line; writes d(means3D 12, means2D 12, opacity 4, scales 12, rotations 16) and
-        # dSH 192 -- or, with the SH Adam inside, no dSH but m, v read and p, m, v written for the 48 SH floats (5 x 192)
-        pb_plain = (277 + 56 + 192) * N
-        pb_fused = (277 + 56) * N + 20 * n_sh
-        alg = {"composite_bwd": 44 * R + 8 * T + 24 * P + 40 * n_vis, "preprocess_fwd": 312 * N, "adam": 28 * n_adam,
-               "preprocess_bwd": pb_fused if sh_fused else pb_plain}
-        for k, nbytes in alg.items():
-            if k in kern and kern[k]["ms_per_step"] > 0:
-                ms_k = kern[k]["ms_per_step"]
-                if k == "preprocess_fwd" and "sh_color" in kern:       # (view-parallel: SH -> RGB runs as a kernel of its own)
-                    ms_k += kern["sh_color"]["ms_per_step"]
-                gbs = nbytes / (ms_k * 1e-3) / 1e9
-                others[k] = {"algorithmic_bytes": nbytes, "achieved": round(gbs, 1), "unit": "GB/s", "frac": round(gbs / HBM_PEAK_GBS, 4)}
-        if "adam" in others:
-            others["adam"]["parameters_updated"] = n_adam
-        if "preprocess_bwd" in others:
-            others["preprocess_bwd"]["includes_fused_sh_adam"] = sh_fused
-            others["preprocess_bwd"]["algorithmic_bytes_without_the_sh_adam"] = pb_plain
-        result = {
-            "metric": f"rendered views/s ({'eval render' if args.render_only else 'full train step'}) "
-                      f"@{args.gaussians / 1e6:g}M Gaussians {args.width}x{args.height}",
-            "value": round(views_per_s, 3), "unit": "views/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "configs[2]: HyperNeRF-like 1M Gaussians, 1352x1014, stage-3 full train step "
-                                   "(deform, raster, L1+SSIM loss, Adam: all HIP kernels)"
-                       if not args.render_only else "configs[2] eval render (forward only)",
-                       "gaussians": args.gaussians, "width": W, "height": H, "keypoints": args.keypoints,
-                       "nearest_num": args.nearest_num, "time_freq": args.time_freq, "iteration": args.iteration,
-                       "tiles": T, "pixels": P, "R": R, "R_before_timed_region": R0, "R_per_gaussian": round(R / max(args.gaussians, 1), 3),
-                       "visible": n_vis, "parallelism": f"view-parallel x{world}",
-                       "ranks_seen_by_rccl": dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1,
-                       "self_launched": os.environ.get("GP_BENCH_SELF_LAUNCHED") == "1",
-                       "gradient_exchange": None if not ts.reducer.enabled else (
-                           ("all-reduce(SUM) of the flat gradient bucket + replicated Adam" if not getattr(ts, "factorised_sh", False) else
-                            "replicated Adam; SH gradients as (dL/dRGB, view direction) factors: one all-gather of 24 B per Gaussian and rank, summed "
-                            "over the views in rank order on every rank (gp_sh_factor_gradient); all-reduce(SUM) of everything else") if not ts.sharded else
-                           "reduce-scatter(SUM) per region -> Adam on 1/N of every region -> asynchronous all-gather of the parameters"
-                           + ("; SH regions: Adam + all-gather on a side stream from the moment their reduce-scatter lands, awaited by the "
-                              "next forward in front of its SH->RGB kernel only" if getattr(ts, "chain_sh", False) else "")
-                           + (" [ONE-rank group, GP_DIST_FORCE_SINGLE: the code path, not a scaling number]" if world == 1 else "")),
-                       "xgmi_bytes_sent_per_rank_per_step": None if world == 1 else (
-                           getattr(ts.reducer, "bytes_sent_per_step", None) or
-                           (int(2 * 4 * ts.bucket.flat.numel() * (world - 1) / world) if not getattr(ts, "factorised_sh", False) else
-                            # the all-reduce of everything but the SH tensors + the factor all-gather (every rank sends its 24 B per Gaussian to world - 1 peers)
-                            int(2 * 4 * (ts.bucket.flat.numel() - pc._features_dc.numel() - pc._features_rest.numel()) * (world - 1) / world)
-                            + 24 * int(pc._features_dc.shape[0]) * (world - 1))),
-                       "exposed_wait_ms_per_step": waits,          # (--time-waits: compute-stream time inside waits for collectives, rank 0)
-                       "step_driver": (f"one library call per step (gp_train_step_run): {getattr(ts, 'fused_steps', 0)} of the steps since the set-up"
-                                       + ("; the per-Gaussian tensors' Adam update rides in the launch of the keypoint MLP's data backward "
-                                          "(kernels_ms.adam = that launch + the MLP tensors' update; no mlp_bwd_data entry)"
-                                          if (getattr(getattr(getattr(ts, "_fused_plan", None), "upd", None), "adam_early_mask", 0) and world == 1) else "")
-                                       if getattr(ts, "fused_steps", 0) else "autograd graph (render -> loss -> backward -> FusedAdam.step)"),
-                       "binning": "exact (R read back every step)" if args.exact_binning else
-                                  f"capacity mode in warm-up and timed steps (no host sync; {preroll} exact-mode set-up steps before the "
-                                  f"warm-up; {getattr(ts, 'redone', 0)} frames repeated after overflow)",
-                       "depth_sort": "32-bit keys, four 8-bit passes" if not getattr(ts, "last_depth_key_promise", None) else
-                                     (f"{ts.last_depth_key_promise[0]}-bit keys above a promised base ({-(-ts.last_depth_key_promise[0] // 8)} passes; the "
-                                      "projection kernel checks the promise, a broken one repeats the frame like a binning overflow; visible depths "
-                                      f"seen in the set-up steps: {_key_depth(ts._key_lo):.3f} .. {_key_depth(ts._key_hi):.3f})"),
-                       "keypoint_weights": "raw_weights / knn_idx are inputs of the step (BASELINE.json north_star); the reference "
-                                           "recomputes them per frame (hash-grid weights model + kNN): see train_step_with_weights_model_ms"},
-            "ms_per_step_without_depth_promise": None if no_promise_ms is None else round(no_promise_ms, 4),
-            "depth_sort_four_pass_ms": None if four_pass_sort_ms is None else round(four_pass_sort_ms, 4),
-            "roofline": roof,
-            "roofline_other_kernels": others,
-            "eval_render_ms_per_view_synced": None if eval_ms is None else round(eval_ms, 3),      # eval.py's own timing loop
-            "eval_render_views_per_s_synced": None if eval_ms is None else round(1000.0 / eval_ms, 2),
-            "eval_render_views_per_s_pipelined_per_gpu": None if eval_fps is None else round(eval_fps, 2),   # SpeculativeRenderer: no host sync per frame
-            "eval_render_views_per_s_back_to_back_exact_mode": None if eval_fps is None else round(eval_fps_exact, 2),   # render() as is (reads R back every frame)
-            "eval_render_frames_rendered_again_after_overflow": None if eval_fps is None else int(eval_again),
-            "kernels_ms": kern,
-        }
-        if roof is not None and world == 1:
-            try:                                 # measured device peaks beside the vendor number; untimed
-                from gaussianprediction_amd import peaks
-                mp = peaks.measure(device, gib=1.0, reps=5, mfma_iters=2048)
-                roof["peak_measured"] = {"stream_copy": mp["copy_GBps"], "stream_read": mp["read_GBps"], "unit": "GB/s"}
-                roof["frac_of_measured_copy"] = round(roof["achieved"] / mp["copy_GBps"], 4)
-                result["device_peaks_measured"] = mp
-            except Exception as e:
-                roof["peak_measured"] = f"failed: {e}"
-        if not args.no_cpu_baseline and world == 1:
+                _lib.check(_lib.lib().gp_debug_option(0, 0), "opt")
+            except Exception:
+                pass
+        if os.path.exists(tf):
             try:
-                result["cpu_baseline"] = cpu_baseline(args, pc, cams, gts, margs)
-            except Exception as e:  # the baseline must never kill the bench line
-                result["cpu_baseline"] = {"value": None, "unit": "views/s", "cores": os.cpu_count(), "kind": "port",
-                                          "sample": f"failed: {e}"}
-        if world == 1 and not args.render_only and not args.no_dense_variant:
-            try:
-                result["dense_variant"] = dense_variant(args, device)
-            except Exception as e:
-                result["dense_variant"] = f"failed: {e}"
-        if world == 1 and not args.render_only and not args.no_weights_model_step:
-            # the step the REFERENCE runs in stage 3 also evaluates the hash-grid weights model and the kNN every frame (and
-            # optimizes the former) [REF scene/gaussian_model.py:257-260,402]; north_star takes their outputs as inputs, so the
-            # headline does not contain them -- this is the same step with them inside, on this package's own kernels
-            try:
-                from gaussianprediction_amd.weights_ops import WeightsModel
-                margs.knn_type, margs.feature_amplify = "hybird", 5.0
-                pc.weights_model = WeightsModel(2 * args.nearest_num, device=device)
-                pc.set_keypoint_weights(None, None)
-                pc.optimizer = None
-                ts2 = TrainStep(pc, cams, gts, args.iteration, lrs=dict(xyz=1.6e-6 * 5.0))
-                for i in range(5):
-                    ts2.step(i)
+                tj = json.load(open(tf))
+                if tj.get("kernel_source_sha16") == kernel_source_stamp():
+                    roof["traffic"] = tj.get("hbm_bytes_per_launch")
+                    # (the same counters read as if every request were a 128-byte one: what the traffic could be at most if the
+                    # gather calibration of the PMC file's header did not hold)
+                    roof["traffic_upper_bound"] = tj.get("hbm_bytes_per_launch_upper_bound")
+                    roof["traffic_source"] = tj.get("source")
+                    vj = tj.get("valu")
+                    if vj:
+                        # the kernel is declared "hbm"-bound by the contract's formula, but what it waits for is the vector
+                        # ALU: the instruction floor (every SIMD issuing one wave64 VALU instruction per 4 cycles) and how busy
+                        # the VALUs were, from the SQ counters of the same kernel source
+                        cycles = avg_ms * 1e-3 * SHADER_CLOCK_GHZ * 1e9
+                        roof["valu_floor_ms"] = round(4.0 * vj["SQ_INSTS_VALU"] / 1024.0 / (SHADER_CLOCK_GHZ * 1e9) * 1e3, 4)
+                        roof["valu_issue_frac"] = round(roof["valu_floor_ms"] / avg_ms, 4)     # the roof the kernel actually runs under
+                        roof["valu_busy"] = round(min(1.0, 4.0 * vj["SQ_ACTIVE_INST_VALU"] / (1024.0 * cycles)), 3)
+                        roof["valu_insts_per_launch"] = int(vj["SQ_INSTS_VALU"])
+                        roof["valu_source"] = vj.get("source")
+                else:
+                    roof["traffic_source"] = "profiles/composite_fwd_traffic.json describes another kernel source: not quoted"
+            except Exception:
+                pass
+    # the other HBM-bound kernels of the step against the same roofline (algorithmic bytes: SURVEY.md 8d / DESIGN.md 4;
+    # durations from the untimed per-kernel pass), reported beside the contract's `roofline` object
+    others = {}
+    N = args.gaussians
+    # Adam: 28 B per parameter the launch ACTUALLY updates (p, g, m, v read; p, m, v written).  In single-view single-rank
+    # steps the two SH tensors (48 of the 59 floats per Gaussian) are updated inside the rasterizer backward instead
+    # (gp_adam_fuse) and their bytes belong to preprocess_bwd's line.
+    sh_fused = bool(getattr(ts, "fuse_sh_adam", False) and not ts.reducer.enabled and ts.batch == 1)
+    sh_ids = {id(pc._features_dc), id(pc._features_rest)}
+    n_adam = sum(int(p.numel()) for p in ts.bucket.params if not (sh_fused and id(p) in sh_ids))
+    n_sh = sum(int(p.numel()) for p in ts.bucket.params if id(p) in sh_ids)
+    # preprocess backward per Gaussian: reads means 12 + scales 12 + rotations 16 + SH 192 + radii 4 + clamp flags 1 + the
+    # 40 useful bytes of its accumulator line; writes d(means3D 12, means2D 12, opacity 4, scales 12, rotations 16) and
+    # dSH 192 -- or, with the SH Adam inside, no dSH but m, v read and p, m, v written for the 48 SH floats (5 x 192)
+    pb_plain = (277 + 56 + 192) * N
+    pb_fused = (277 + 56) * N + 20 * n_sh
+    alg = {"composite_bwd": 44 * R + 8 * T + 24 * P + 40 * n_vis, "preprocess_fwd": 312 * N, "adam": 28 * n_adam,
+           "preprocess_bwd": pb_fused if sh_fused else pb_plain}
+    for k, nbytes in alg.items():
+        if k in kern and kern[k]["ms_per_step"] > 0:
+            ms_k = kern[k]["ms_per_step"]
+            if k == "preprocess_fwd" and "sh_color" in kern:       # (view-parallel: SH -> RGB runs as a kernel of its own)
+                ms_k += kern["sh_color"]["ms_per_step"]
+            gbs = nbytes / (ms_k * 1e-3) / 1e9
+            others[k] = {"algorithmic_bytes": nbytes, "achieved": round(gbs, 1), "unit": "GB/s", "frac": round(gbs / HBM_PEAK_GBS, 4)}
+    if "adam" in others:
+        others["adam"]["parameters_updated"] = n_adam
+    if "preprocess_bwd" in others:
+        others["preprocess_bwd"]["includes_fused_sh_adam"] = sh_fused
+        others["preprocess_bwd"]["algorithmic_bytes_without_the_sh_adam"] = pb_plain
+    result["config"].update({"tiles": T, "pixels": P, "R": R, "R_before_timed_region": R0, "R_per_gaussian": round(R / max(args.gaussians, 1), 3),
+                             "visible": n_vis})
+    result.update({
+        "ms_per_step_without_depth_promise": None if full.no_promise_ms is None else round(full.no_promise_ms, 4),
+        "depth_sort_four_pass_ms": None if full.four_pass_sort_ms is None else round(full.four_pass_sort_ms, 4),
+        "roofline": roof,
+        "roofline_other_kernels": others,
+        "eval_render_ms_per_view_synced": None if full.eval_ms is None else round(full.eval_ms, 3),      # eval.py's own timing loop
+        "eval_render_views_per_s_synced": None if full.eval_ms is None else round(1000.0 / full.eval_ms, 2),
+        "eval_render_views_per_s_pipelined_per_gpu": None if full.eval_fps is None else round(full.eval_fps, 2),   # SpeculativeRenderer: no host sync per frame
+        "eval_render_views_per_s_back_to_back_exact_mode": None if full.eval_fps is None else round(full.eval_fps_exact, 2),   # render() as is (reads R back every frame)
+        "eval_render_frames_rendered_again_after_overflow": None if full.eval_fps is None else int(full.eval_again),
+        "kernels_ms": kern,
+    })
+    if roof is not None and world == 1:
+        try:                                 # measured device peaks beside the vendor number (SURVEY.md 8d); untimed
+            from gaussianprediction_amd import peaks
+            mp = peaks.measure(device, gib=1.0, reps=5, mfma_iters=2048)
+            roof["peak_measured"] = {"stream_copy": mp["copy_GBps"], "stream_read": mp["read_GBps"], "unit": "GB/s"}
+            roof["frac_of_measured_copy"] = round(roof["achieved"] / mp["copy_GBps"], 4)
+            result["device_peaks_measured"] = mp
+        except Exception as e:
+            roof["peak_measured"] = f"failed: {e}"
+    if not args.no_cpu_baseline and world == 1:
+        try:
+            result["cpu_baseline"] = cpu_baseline(args, pc, cams, gts, margs)
+        except Exception as e:  # the baseline must never kill the bench line
+            result["cpu_baseline"] = {"value": None, "unit": "views/s", "cores": os.cpu_count(), "kind": "port",
+                                      "sample": f"failed: {e}"}
+    if world == 1 and not args.render_only and not args.no_dense_variant:
+        try:
+            result["dense_variant"] = dense_variant(args, device)
+        except Exception as e:
+            result["dense_variant"] = f"failed: {e}"
+    if world == 1 and not args.render_only and not args.no_weights_model_step:
+        # the step the REFERENCE runs in stage 3 also evaluates the hash-grid weights model and the kNN every frame (and
+        # optimizes the former) [REF scene/gaussian_model.py:257-260,402]; north_star takes their outputs as inputs, so the
+        # headline does not contain them -- this is the same step with them inside, on this package's own kernels
+        try:
+            from gaussianprediction_amd.weights_ops import WeightsModel
+            margs.knn_type, margs.feature_amplify = "hybird", 5.0
+            pc.weights_model = WeightsModel(2 * args.nearest_num, device=device)
+            pc.set_keypoint_weights(None, None)
+            pc.optimizer = None
+            ts2 = TrainStep(pc, cams, gts, args.iteration, lrs=dict(xyz=1.6e-6 * 5.0))
+            for i in range(5):
+                ts2.step(i)
+            torch.cuda.synchronize()
+            host = []
+            with no_gc():
+                t1 = time.perf_counter()
+                for i in range(20):
+                    th = time.perf_counter()
+                    ts2.step(5 + i)
+                    host.append(time.perf_counter() - th)
                 torch.cuda.synchronize()
-                host = []
-                with no_gc():
-                    t1 = time.perf_counter()
-                    for i in range(20):
-                        th = time.perf_counter()
-                        ts2.step(5 + i)
-                        host.append(time.perf_counter() - th)
-                    torch.cuda.synchronize()
-                    result["train_step_with_weights_model_ms"] = round(1000.0 * (time.perf_counter() - t1) / 20, 3)
-                if os.environ.get("GP_BENCH_DEBUG"):
-                    ms = torch.cuda.memory_stats()
-                    print("[weights-model leg] host ms per step:", [round(1e3 * h, 2) for h in host], "reserved GB",
-                          round(torch.cuda.memory_reserved() / 2**30, 2), "alloc retries", ms.get("num_alloc_retries"),
-                          "device mallocs", ms.get("num_device_alloc"), "device frees", ms.get("num_device_free"), file=sys.stderr, flush=True)
-            except Exception as e:
-                result["train_step_with_weights_model_ms"] = f"failed: {e}"
-        print(json.dumps(result), flush=True)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+                result["train_step_with_weights_model_ms"] = round(1000.0 * (time.perf_counter() - t1) / 20, 3)
+            if os.environ.get("GP_BENCH_DEBUG"):
+                ms = torch.cuda.memory_stats()
+                print("[weights-model leg] host ms per step:", [round(1e3 * h, 2) for h in host], "reserved GB",
+                      round(torch.cuda.memory_reserved() / 2**30, 2), "alloc retries", ms.get("num_alloc_retries"),
+                      "device mallocs", ms.get("num_device_alloc"), "device frees", ms.get("num_device_free"), file=sys.stderr, flush=True)
+        except Exception as e:
+            result["train_step_with_weights_model_ms"] = f"failed: {e}"
 
 
 if __name__ == "__main__":

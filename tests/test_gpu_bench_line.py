@@ -1,11 +1,13 @@
 """-m gpu: the ONE JSON line bench.py prints -- the fields the driver and the judge read (metric / value / unit / n_gpus / steps / warmup /
 ms_per_step / higher_is_better / scaling / vs_baseline / dtype / data / config.workload, the `roofline` and `cpu_baseline` objects) are
-present, typed and mutually consistent.  Run on a small scene (the contract is the same code path as the headline run)."""
+present, typed and mutually consistent (--full: the secondary measurements too; a plain run: the headline fields and --dump-outputs).
+Run on a small scene (the contract is the same code path as the headline run)."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -25,7 +27,7 @@ def _bench(*extra):
 
 
 def test_bench_prints_one_well_formed_line():
-    d = _bench("--no-weights-model-step")
+    d = _bench("--full", "--no-weights-model-step")
     assert d["metric"].startswith("rendered views/s") and d["unit"] == "views/s" and d["higher_is_better"] is True
     assert d["n_gpus"] == 1 and d["steps"] == 12 and d["warmup"] == 3 and d["scaling"] == "weak" and d["data"] == "synthetic"
     assert d["dtype"] == "f32" and d["vs_baseline"] is None
@@ -51,3 +53,25 @@ def test_bench_prints_one_well_formed_line():
     # the headline's depth sort runs under a key-range promise that depends on the scene: the same step without it is in the record
     if "promised base" in d["config"]["depth_sort"]:
         assert d["ms_per_step_without_depth_promise"] > 0 and d["depth_sort_four_pass_ms"] > 0
+
+
+def test_plain_run_prints_the_headline_and_dumps_the_last_step_the_same_in_every_run(tmp_path):
+    runs = [_bench("--dump-outputs", str(tmp_path / r)) for r in ("a", "b")]
+    for d in runs:
+        assert d["metric"].startswith("rendered views/s") and d["unit"] == "views/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert d["steps"] == 12 and d["warmup"] == 3 and d["ms_per_step"] > 0
+        assert abs(d["value"] - 1000.0 / d["ms_per_step"]) <= 0.01 * d["value"]
+        for k in ("roofline", "kernels_ms", "cpu_baseline", "dense_variant", "train_step_with_weights_model_ms"):
+            assert k not in d, k                                                      # --full only
+    a, b = ({f.name[:-4]: np.load(f) for f in (tmp_path / r).iterdir()} for r in ("a", "b"))
+    assert set(a) == {"loss", "render", "depth", "radii", "tidx", "visibility_filter", "viewspace_points_grad"} == set(b)
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 64 * 10**6
+    assert all(v.dtype in (np.float32, np.float64) and np.isfinite(v).all() for v in a.values())
+    assert a["render"].shape == (3, 304, 400) and a["loss"].shape == () and float(a["loss"]) > 0
+    assert a["radii"].shape == (32768,) and a["viewspace_points_grad"].shape == (32768, 3)       # (a seeded sample of the 60 000 rows)
+    # the same arguments, the same outputs: the forward's bit for bit, the backward's up to the summation order of its float atomics
+    for k in ("render", "depth", "radii", "tidx", "visibility_filter"):
+        assert np.array_equal(a[k], b[k]), k
+    assert abs(float(a["loss"]) - float(b["loss"])) <= 1e-5 * float(a["loss"])
+    g = a["viewspace_points_grad"]
+    assert np.abs(g - b["viewspace_points_grad"]).max() <= 1e-4 * np.abs(g).max() and np.abs(g).max() > 0

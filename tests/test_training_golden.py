@@ -33,8 +33,16 @@ def test_learning_rate_schedules_match_the_reference():
 
 def test_build_rotation_and_inverse_sigmoid_match_the_reference():
     c = np.load(os.path.join(G, "cov3d.npz"))
+    # The reference's R is its own float32 arithmetic: 2.9 eps from the exact rotation.  The float32 result here lands within ~4 eps of the
+    # exact one as well, but where depends on the host CPU (bit-identical to the fixture on the x86 host that made it, 4 eps away on an
+    # AMD EPYC host).  So: the formula evaluated in float64 -- the same on every host -- within 4 eps of the reference, and the float32
+    # path within 8 eps (two float32 evaluations, each within 4 eps of the exact value).
+    eps = float(np.finfo(np.float32).eps)
+    R64 = training.build_rotation(torch.tensor(c["quats"], dtype=torch.float64))
+    np.testing.assert_allclose(R64.numpy(), c["R"], rtol=0, atol=4 * eps)
     R = training.build_rotation(torch.tensor(c["quats"]))
-    np.testing.assert_allclose(R.numpy(), c["R"], rtol=0, atol=2e-7)
+    assert R.dtype == torch.float32
+    np.testing.assert_allclose(R.numpy(), c["R"], rtol=0, atol=8 * eps)
     g = np.load(os.path.join(G, "training.npz"))
     x = torch.tensor(g["inv_sig_x"])
     np.testing.assert_allclose(torch.log(x / (1 - x)).numpy(), g["inv_sig_y"], rtol=1e-6)

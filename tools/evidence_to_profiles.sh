@@ -10,7 +10,7 @@ python - "$IN" "$TAG" <<'PY'
 import csv, sys
 inp, tag = sys.argv[1], sys.argv[2]
 rows = list(csv.DictReader(open(f"{inp}/stats/s_kernel_stats.csv")))
-out = ["# rocprofv3 --kernel-trace --stats -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-weights-model-step   (MI355X)",
+out = ["# rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-weights-model-step   (MI355X)",
        f"{'kernel':62s} {'calls':>6s} {'total_ms':>10s} {'avg_us':>10s} {'min_us':>9s} {'max_us':>9s} {'pct':>6s}"]
 for r in rows[:48]:
     out.append(f"{r['Name'][:62]:62s} {int(r['Calls']):6d} {float(r['TotalDurationNs'])/1e6:10.3f} {float(r['AverageNs'])/1e3:10.2f} "

@@ -78,7 +78,7 @@ def main(dfetch, dwrite, cfetch, cwrite, out_txt, out_json):
         rows.append((1024 * (fac * f + w) / 1e6, k, n, f, w, fac))
     rows.sort(reverse=True)
     with open(out_txt, "w") as o:
-        o.write("# rocprofv3 --pmc FETCH_SIZE  and (separate pass)  --pmc WRITE_SIZE  -- python bench.py --steps 3 --warmup 2 --no-cpu-baseline\n")
+        o.write("# rocprofv3 --pmc FETCH_SIZE  and (separate pass)  --pmc WRITE_SIZE  -- python bench.py --full --steps 3 --warmup 2 --no-cpu-baseline\n")
         o.write("# units: KiB per dispatch (counter value); hbm_bytes = 1024 * (factor * FETCH_SIZE + WRITE_SIZE)\n")
         o.write("# calibration (tools/pmc_calibrate.py, same box, separate passes): FETCH_SIZE*1024 / bytes requested --\n")
         for name, c in cal.items():
