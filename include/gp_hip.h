@@ -542,6 +542,33 @@ int gp_knn3_mean_dist2(int64_t n, const float* xyz /*[n,3]*/, float* out /*[n]*/
  * batch [REF utils/fps.py:71-88, scene/gaussian_model.py:196-212 get_new_kpts]. */
 int gp_furthest_point_sampling(int64_t n, const float* xyz, int64_t m, int32_t* idx_out, float* tmp_dist, gp_stream_t stream);
 
+/* General k-nearest neighbours (csrc/knn_kernels.hip): replaces pytorch3d.ops.knn_points [REF scene/gaussian_model.py:208,
+ * utils/loss_utils.py:36,43], frnn.frnn_grid_points [REF scene/gaussian_model.py:113,117] and pointops' knnquery_cuda.
+ * Queries p1[B,P1,D] against candidates p2[B,P2,D] (fp32, contiguous; 1 <= D <= 64, B <= 65535, P1, P2 < 2^31); lengths1 / lengths2
+ * (optional, int64[B]) are the live rows of each batch.  dists[B,P1,K] / idx[B,P1,K] (int64, index within the batch) = the K nearest
+ * (1 <= K <= 32) sorted by ascending distance, ties to the lower index.  Distance: sum over the dimensions in order of (x - y)^2
+ * (norm 2, the SQUARED distance) or |x - y| (norm 1); no inner-product expansion.  Slots beyond lengths2[b], rows beyond lengths1[b]
+ * and neighbours with distance > r2_max (INFINITY = no cutoff) receive (pad_dist, pad_idx).  splits: 0 = automatic; n > 0 cuts the
+ * candidates into n pieces searched by workgroups of their own and merged (TEMP scratch from `alloc`, which may be NULL when no split
+ * happens).  The result does not depend on splits. */
+int gp_knn_points(int64_t B, int64_t P1, int64_t P2, int32_t D, const float* p1, const float* p2, const int64_t* lengths1,
+                  const int64_t* lengths2, int32_t K, int32_t norm, float r2_max, int32_t splits, int64_t pad_idx, float pad_dist,
+                  float* dists, int64_t* idx, gp_alloc_fn alloc, void* alloc_ctx, gp_stream_t stream);
+/* grad_p1[B,P1,D] += and grad_p2[B,P2,D] += (atomics) the gradient of sum(dists * grad_dists) for the neighbours in idx (as written by
+ * gp_knn_points): 2 (p1 - p2) for norm 2, sign(p1 - p2) for norm 1, the negative for p2.  Slots whose idx lies outside
+ * [0, lengths2[b]) and rows beyond lengths1[b] contribute nothing: run the forward with pad_idx = -1 to keep padded slots out.
+ * Either gradient pointer may be NULL. */
+int gp_knn_points_backward(int64_t B, int64_t P1, int64_t P2, int32_t D, const float* p1, const float* p2, const int64_t* lengths1,
+                           const int64_t* lengths2, const int64_t* idx, int32_t K, int32_t norm, const float* grad_dists, float* grad_p1,
+                           float* grad_p2, gp_stream_t stream);
+/* Batched furthest-point sampling with pointops' furthestsampling_cuda semantics [REF utils/fps.py:71-88]: offset / new_offset
+ * (int32[b], device) are cumulative ends; batch i samples points [offset[i-1], offset[i]) of xyz[n_total,3] into
+ * idx[new_offset[i-1] .. new_offset[i]) (int32, GLOBAL indices), starting at its own first point.  The selection and tie rule are
+ * gp_furthest_point_sampling's (b = 1 is bit-identical to it).  tmp: n_total floats of scratch; m_total: the length of idx.  A batch
+ * whose offsets are not increasing or exceed n_total / m_total is skipped. */
+int gp_furthest_point_sampling_batched(int32_t b, const int32_t* offset, const int32_t* new_offset, int64_t n_total, int64_t m_total,
+                                       const float* xyz, float* tmp, int32_t* idx, gp_stream_t stream);
+
 /* ---- measurement ----------------------------------------------------------------------------- */
 /* gp_profile_enable(level): 0 = off, 1 = bracket only the roofline kernel (composite forward), 2 = every
  * kernel.  When enabled, the library brackets kernels with hipEvent pairs recorded on the launch stream.
@@ -605,8 +632,9 @@ int gp_sh_factor_gradient(int64_t n, int32_t world, const float* factors, int32_
  * gp_knn_keypoints' `order`, GP_LOSS_SUM_SLOTS per image size); 3 = round 4 (gp_abi_version itself); 4 = round 4 (gp_mlp_params.packed, gp_blend_args.knn_idx16, gp_knn_keypoints' signature,
  * gp_adam_step_multi_steps); 5 = round 5 (gp_train_step_run and its three structs);
  * 6 = round 6 (gp_mlp16_pack / gp_mlp16_packed_elems, gp_loss_l1_ssim_fused, gp_sh_factor_gradient; the ReLU words gp_mlp16_forward hands to gp_mlp16_backward changed layout);
- * 7 = round 6, last session (gp_mlp_params.scratch + gp_mlp_scratch_bytes, gp_raster_settings.raw_activations, the saved 16-bit tensors' extent padded to 128 rows). */
-#define GP_ABI_VERSION 7
+ * 7 = round 6, last session (gp_mlp_params.scratch + gp_mlp_scratch_bytes, gp_raster_settings.raw_activations, the saved 16-bit tensors' extent padded to 128 rows);
+ * 8 = gp_knn_points, gp_knn_points_backward, gp_furthest_point_sampling_batched (the reference's CUDA-extension shims). */
+#define GP_ABI_VERSION 8
 int gp_abi_version(void);
 
 #ifdef __cplusplus
