@@ -1,6 +1,7 @@
 // deform_kernels.h -- device-side argument structs + kernel declarations (definitions in deform_kernels.hip)
 #pragma once
 #include "gp_common.h"
+#include "loss_adam_kernels.h"     // BlendRideDev
 
 struct MlpDev {
     long rows;
@@ -92,6 +93,13 @@ __global__ __launch_bounds__(256) void gp_blend_bwd8_i16_kernel(BlendDev a, cons
                                                            const float* __restrict__ g_q_t, float* __restrict__ g_delta,
                                                            float* __restrict__ g_raw_w, float* __restrict__ g_xyz,
                                                            float* __restrict__ g_rot, float* __restrict__ partial);
+// (the nn = 6 / 8 kernels with the fused step's riders in front of the blend's workgroups: loss_adam_kernels.h, GpBlendRider)
+#define GP_BB_RIDE_ARGS BlendRideDev r, BlendDev a, const float* __restrict__ g_xyz_t, const float* __restrict__ g_q_t, \
+    float* __restrict__ g_delta, float* __restrict__ g_raw_w, float* __restrict__ g_xyz, float* __restrict__ g_rot, float* __restrict__ partial
+__global__ __launch_bounds__(256) void gp_blend_bwd6_ride_kernel(GP_BB_RIDE_ARGS);
+__global__ __launch_bounds__(256) void gp_blend_bwd8_ride_kernel(GP_BB_RIDE_ARGS);
+__global__ __launch_bounds__(256) void gp_blend_bwd6_i16_ride_kernel(GP_BB_RIDE_ARGS);
+__global__ __launch_bounds__(256) void gp_blend_bwd8_i16_ride_kernel(GP_BB_RIDE_ARGS);
 __global__ __launch_bounds__(1024) void gp_blend_bwd_reduce_kernel(const float* __restrict__ partial, int nblocks, int KA,
                                                                   int od, float* __restrict__ g_delta);
 __global__ __launch_bounds__(256) void gp_act_fwd_kernel(long n, const float* __restrict__ scaling_raw,

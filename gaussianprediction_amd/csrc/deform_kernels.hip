@@ -808,7 +808,8 @@ template <int NN, bool I16 = false>
 __device__ __forceinline__ void blend_bwd_body(BlendDev a, const float* __restrict__ g_xyz_t,
                                                const float* __restrict__ g_q_t, float* __restrict__ g_delta,
                                                float* __restrict__ g_raw_w, float* __restrict__ g_xyz,
-                                               float* __restrict__ g_rot, float* __restrict__ partial) {
+                                               float* __restrict__ g_rot, float* __restrict__ partial, const unsigned bid,
+                                               const unsigned nblk) {     // workgroup bid of nblk (a launch with riders: less than the grid)
     extern __shared__ float s_dyn[];
     const int od = a.out_dim;
     const int nn = NN > 0 ? NN : a.nn;
@@ -842,7 +843,7 @@ __device__ __forceinline__ void blend_bwd_body(BlendDev a, const float* __restri
         }
     }
     const long chunks = (a.N + 255) / 256;
-    for (long c = blockIdx.x; c < chunks; c += gridDim.x) {
+    for (long c = bid; c < chunks; c += nblk) {
         const long i = c * 256 + tid;
         const bool live = i < a.N;
         if (nn > 0) {
@@ -1036,17 +1037,41 @@ __device__ __forceinline__ void blend_bwd_body(BlendDev a, const float* __restri
             }
         }
         __syncthreads();
-        for (int e = tid; e < KA; e += 256) partial[(size_t)blockIdx.x * KA + e] = s_acc[e];
+        for (int e = tid; e < KA; e += 256) partial[(size_t)bid * KA + e] = s_acc[e];
     }
 }
 
 #define BB_ARGS BlendDev a, const float* __restrict__ g_xyz_t, const float* __restrict__ g_q_t, float* __restrict__ g_delta, \
     float* __restrict__ g_raw_w, float* __restrict__ g_xyz, float* __restrict__ g_rot, float* __restrict__ partial
-__global__ __launch_bounds__(256) void gp_blend_bwd_kernel(BB_ARGS) { blend_bwd_body<0>(a, g_xyz_t, g_q_t, g_delta, g_raw_w, g_xyz, g_rot, partial); }
-__global__ __launch_bounds__(256) void gp_blend_bwd6_kernel(BB_ARGS) { blend_bwd_body<6>(a, g_xyz_t, g_q_t, g_delta, g_raw_w, g_xyz, g_rot, partial); }
-__global__ __launch_bounds__(256) void gp_blend_bwd8_kernel(BB_ARGS) { blend_bwd_body<8>(a, g_xyz_t, g_q_t, g_delta, g_raw_w, g_xyz, g_rot, partial); }
-__global__ __launch_bounds__(256) void gp_blend_bwd6_i16_kernel(BB_ARGS) { blend_bwd_body<6, true>(a, g_xyz_t, g_q_t, g_delta, g_raw_w, g_xyz, g_rot, partial); }
-__global__ __launch_bounds__(256) void gp_blend_bwd8_i16_kernel(BB_ARGS) { blend_bwd_body<8, true>(a, g_xyz_t, g_q_t, g_delta, g_raw_w, g_xyz, g_rot, partial); }
+__global__ __launch_bounds__(256) void gp_blend_bwd_kernel(BB_ARGS) { blend_bwd_body<0>(a, g_xyz_t, g_q_t, g_delta, g_raw_w, g_xyz, g_rot, partial, blockIdx.x, gridDim.x); }
+__global__ __launch_bounds__(256) void gp_blend_bwd6_kernel(BB_ARGS) { blend_bwd_body<6>(a, g_xyz_t, g_q_t, g_delta, g_raw_w, g_xyz, g_rot, partial, blockIdx.x, gridDim.x); }
+__global__ __launch_bounds__(256) void gp_blend_bwd8_kernel(BB_ARGS) { blend_bwd_body<8>(a, g_xyz_t, g_q_t, g_delta, g_raw_w, g_xyz, g_rot, partial, blockIdx.x, gridDim.x); }
+__global__ __launch_bounds__(256) void gp_blend_bwd6_i16_kernel(BB_ARGS) { blend_bwd_body<6, true>(a, g_xyz_t, g_q_t, g_delta, g_raw_w, g_xyz, g_rot, partial, blockIdx.x, gridDim.x); }
+__global__ __launch_bounds__(256) void gp_blend_bwd8_i16_kernel(BB_ARGS) { blend_bwd_body<8, true>(a, g_xyz_t, g_q_t, g_delta, g_raw_w, g_xyz, g_rot, partial, blockIdx.x, gridDim.x); }
+
+// The same launch with riders of the fused train step IN FRONT of the blend's workgroups (loss_adam_kernels.h, GpBlendRider): workgroup 0
+// the loss finalize, then one Adam chunk per workgroup, then the blend on the rest of the grid.  Riders go first because workgroups are
+// dispatched in blockIdx order: behind a grid that fills every CU they would start when the blend is over.  No rider waits for, or
+// signals, anything: they are independent of the blend's work.  The riders' few bytes of LDS are the blend's dynamic block.
+template <int NN, bool I16>
+__device__ __forceinline__ void blend_bwd_ride_body(const BlendRideDev& r, BB_ARGS) {
+    const unsigned riders = r.fin_blocks + r.adam_chunks;
+    if (blockIdx.x < riders) {
+        if (blockIdx.x < r.fin_blocks) {
+            extern __shared__ float s_dyn[];
+            double* s_tot = (double*)(((uintptr_t)s_dyn + 7) & ~(uintptr_t)7);
+            loss_finalize_body(r.fin, (float*)(s_tot + 8), s_tot);
+        } else {
+            adam_chunk_body<256>(r.t, blockIdx.x - r.fin_blocks, threadIdx.x, r.b1, r.b2, r.eps, r.zero_grad, r.skip_flag);
+        }
+        return;
+    }
+    blend_bwd_body<NN, I16>(a, g_xyz_t, g_q_t, g_delta, g_raw_w, g_xyz, g_rot, partial, blockIdx.x - riders, gridDim.x - riders);
+}
+__global__ __launch_bounds__(256) void gp_blend_bwd6_ride_kernel(BlendRideDev r, BB_ARGS) { blend_bwd_ride_body<6, false>(r, a, g_xyz_t, g_q_t, g_delta, g_raw_w, g_xyz, g_rot, partial); }
+__global__ __launch_bounds__(256) void gp_blend_bwd8_ride_kernel(BlendRideDev r, BB_ARGS) { blend_bwd_ride_body<8, false>(r, a, g_xyz_t, g_q_t, g_delta, g_raw_w, g_xyz, g_rot, partial); }
+__global__ __launch_bounds__(256) void gp_blend_bwd6_i16_ride_kernel(BlendRideDev r, BB_ARGS) { blend_bwd_ride_body<6, true>(r, a, g_xyz_t, g_q_t, g_delta, g_raw_w, g_xyz, g_rot, partial); }
+__global__ __launch_bounds__(256) void gp_blend_bwd8_i16_ride_kernel(BlendRideDev r, BB_ARGS) { blend_bwd_ride_body<8, true>(r, a, g_xyz_t, g_q_t, g_delta, g_raw_w, g_xyz, g_rot, partial); }
 
 // stage 2: g_delta[k, c] = sum over workgroups (deterministic, no atomics).  64 elements per workgroup, the
 // workgroup's 16 waves split the partials (four independent sums each) and meet in LDS.

@@ -293,8 +293,19 @@ extern "C" int gp_blend_backward(const gp_blend_args* a, const float* dL_dxyz_t,
     if (make_blend(a, b)) return 1;
     if (b.N == 0) return 0;
     if (!dL_dxyz_t || !dL_dq_t || !dL_ddelta || !dL_dxyz || !dL_drot) GP_FAIL("null argument");     // dL_draw_w may be NULL
+    const bool al = (((uintptr_t)b.raw_w | (uintptr_t)b.knn | (uintptr_t)dL_draw_w) & 15) == 0;
+    const bool i16 = b.knn16 != nullptr;
+    // riders of the fused step (loss_adam_kernels.h, GpBlendRider; armed by gp_train_step_run only): the nn = 6 / 8 kernels carry them,
+    // what this call does not carry stays armed for gp_blend_rider_flush
+    GpBlendRider* rider = gp_blend_rider_slot();
+    const bool ride = (rider->fin_armed || rider->adam.armed) && al && (b.nn == 6 || b.nn == 8);
+    const unsigned adam_chunks = ride && rider->adam.armed ? rider->adam.chunks : 0u;
     unsigned blocks = gp_blocks((size_t)b.N, 256);
-    if (b.nn > 0 && blocks > 1024) blocks = 1024;   // persistent: four workgroups per CU (LDS), their partials are summed by the reduce kernel
+    // persistent: four workgroups per CU (LDS), their partials are summed by the reduce kernel.  Beside Adam chunks THREE per CU: the
+    // partition is static (workgroup b owns chunks b, b + grid, ...), so a workgroup that starts behind a rider finishes late by as much
+    // (measured, profiles/step_riders_ab.txt: 1 024 beside the chunks 1.079 ms per step, 768: 1.068)
+    const unsigned cap = adam_chunks > 0 ? 768u : 1024u;
+    if (b.nn > 0 && blocks > cap) blocks = cap;
     // acc[K*7] | delta[K*od] | cnt[K] | base[K+1] | g[7*256] | inv[K] | w[256*2*nn] | sorted u16 [256*nn]
     const size_t lds = b.nn > 0 ? ((size_t)b.K * (7 + b.out_dim + 3) + 1 + 256 * 7 + 256 * 2 * (size_t)b.nn) * 4 + 256 * (size_t)b.nn * 2 + 16 : 256 * 8 * 4;
     if (lds > 64 * 1024) GP_FAIL("keypoint blend backward: K = %ld, nn = %d needs %zu B of LDS (> 64 KiB)", (long)b.K, b.nn, lds);
@@ -306,12 +317,25 @@ extern "C" int gp_blend_backward(const gp_blend_args* a, const float* dL_dxyz_t,
         if (!partial) GP_FAIL("allocator returned NULL for TEMP");
     }
     { GpProfScope _p("blend_bwd", (hipStream_t)stream_);
-    const bool al = (((uintptr_t)b.raw_w | (uintptr_t)b.knn | (uintptr_t)dL_draw_w) & 15) == 0;
-    const bool i16 = b.knn16 != nullptr;
-    hipLaunchKernelGGL(b.nn == 6 && al ? (i16 ? gp_blend_bwd6_i16_kernel : gp_blend_bwd6_kernel)
-                       : b.nn == 8 && al ? (i16 ? gp_blend_bwd8_i16_kernel : gp_blend_bwd8_kernel) : gp_blend_bwd_kernel,
-                       dim3(blocks), dim3(256), lds, (hipStream_t)stream_, b, dL_dxyz_t, dL_dq_t, dL_ddelta,
-                       dL_draw_w, dL_dxyz, dL_drot, partial);
+    if (ride) {
+        BlendRideDev r;
+        memset(&r, 0, sizeof(r));
+        if (adam_chunks) {
+            r.t = rider->adam.t; r.b1 = rider->adam.b1; r.b2 = rider->adam.b2; r.eps = rider->adam.eps; r.zero_grad = rider->adam.zero_grad;
+            r.skip_flag = rider->adam.skip_flag; r.adam_chunks = adam_chunks;
+        }
+        if (rider->fin_armed) { r.fin = rider->fin; r.fin_blocks = 1; }
+        gp_blend_rider_disarm();
+        hipLaunchKernelGGL(b.nn == 6 ? (i16 ? gp_blend_bwd6_i16_ride_kernel : gp_blend_bwd6_ride_kernel)
+                                     : (i16 ? gp_blend_bwd8_i16_ride_kernel : gp_blend_bwd8_ride_kernel),
+                           dim3(r.fin_blocks + r.adam_chunks + blocks), dim3(256), lds, (hipStream_t)stream_, r, b, dL_dxyz_t, dL_dq_t, dL_ddelta,
+                           dL_draw_w, dL_dxyz, dL_drot, partial);
+    } else {
+        hipLaunchKernelGGL(b.nn == 6 && al ? (i16 ? gp_blend_bwd6_i16_kernel : gp_blend_bwd6_kernel)
+                           : b.nn == 8 && al ? (i16 ? gp_blend_bwd8_i16_kernel : gp_blend_bwd8_kernel) : gp_blend_bwd_kernel,
+                           dim3(blocks), dim3(256), lds, (hipStream_t)stream_, b, dL_dxyz_t, dL_dq_t, dL_ddelta,
+                           dL_draw_w, dL_dxyz, dL_drot, partial);
+    }
     GP_LAUNCH_CHECK();
     if (b.nn > 0) {
         hipLaunchKernelGGL(gp_blend_bwd_reduce_kernel, dim3(gp_blocks((size_t)KA, 64)), dim3(1024), 0, (hipStream_t)stream_, partial,

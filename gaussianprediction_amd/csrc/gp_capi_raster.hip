@@ -3,6 +3,7 @@
 // kernels of raster_kernels.hip / sort_scan.hip on the caller's stream.
 #include "gp_common.h"
 #include "raster_kernels.h"
+#include "loss_adam_kernels.h"     // GpLossPrologue
 #include <stdlib.h>
 #include <atomic>
 
@@ -295,6 +296,39 @@ extern "C" int gp_raster_forward(const gp_raster_settings* st, const gp_raster_i
     return 0;
 }
 
+// The backward's TEMP block (accumulators + tile order) handed out BEFORE the backward: gp_train_step_run lets the fused loss launch carry
+// the prologue (loss_adam_kernels.h, GpLossPrologue), and the gp_raster_backward call for the same saved state finds the block here.
+struct GpBwdPrepared {
+    const void* image;      // saved->image of the forward the block belongs to
+    float* acc;
+    size_t acc_floats;
+    bool armed;
+};
+static GpBwdPrepared* bwd_prepared_slot() {
+    static thread_local GpBwdPrepared slot = {};
+    return &slot;
+}
+void gp_raster_backward_unprepare() { bwd_prepared_slot()->armed = false; }
+// pro->armed stays false where the stand-alone prologue has to run (nothing rendered, nothing saved)
+int gp_raster_backward_prepare(const gp_raster_settings* st, const gp_raster_inputs* in, const gp_raster_saved* saved, gp_alloc_fn alloc,
+                               void* alloc_ctx, GpLossPrologue* pro) {
+    bwd_prepared_slot()->armed = false;
+    pro->armed = false;
+    RasterDims d;
+    if (make_dims(st, in, d)) return 1;
+    const size_t N = (size_t)d.N, T = (size_t)d.gx * d.gy, P = (size_t)d.W * d.H;
+    if (N == 0 || !saved || !saved->image || saved->num_rendered <= 0 || !alloc) return 0;
+    ImageLayout il(saved->image, T, P);
+    const size_t acc_floats = (size_t)GP_ACC_STRIDE * N;
+    float* acc = (float*)alloc(alloc_ctx, GP_BUF_TEMP, gp_align_up(acc_floats * 4, 256) + gp_align_up(T * 4, 256));
+    if (!acc) GP_FAIL("allocator returned NULL for TEMP");
+    pro->ranges = il.ranges; pro->tile_work = il.tile_work; pro->T = (int)T;
+    pro->order = (uint32_t*)((char*)acc + gp_align_up(acc_floats * 4, 256));
+    pro->acc = acc; pro->acc_floats = acc_floats; pro->armed = true;
+    *bwd_prepared_slot() = GpBwdPrepared{saved->image, acc, acc_floats, true};
+    return 0;
+}
+
 extern "C" int gp_raster_backward(const gp_raster_settings* st, const gp_raster_inputs* in, const gp_raster_outputs* fwd,
                                   const gp_raster_saved* saved, const float* dL_dcolor, const float* dL_ddepth,
                                   gp_raster_grads* g, gp_alloc_fn alloc, void* alloc_ctx, gp_stream_t stream_) {
@@ -332,10 +366,15 @@ extern "C" int gp_raster_backward(const gp_raster_settings* st, const gp_raster_
     if (R > 0 && !point_list) GP_FAIL("saved binning state missing");
 
     const size_t acc_floats = (size_t)GP_ACC_STRIDE * N;
-    float* acc = (float*)alloc(alloc_ctx, GP_BUF_TEMP, gp_align_up(acc_floats * 4, 256) + gp_align_up(T * 4, 256));
+    // (gp_train_step_run: the block was obtained ahead of the loss, and the loss launch carried the prologue -- gp_raster_backward_prepare)
+    GpBwdPrepared* pre = bwd_prepared_slot();
+    const bool prepared = pre->armed && pre->image == saved->image && pre->acc_floats == acc_floats && R > 0;
+    pre->armed = false;
+    float* acc = prepared ? pre->acc : (float*)alloc(alloc_ctx, GP_BUF_TEMP, gp_align_up(acc_floats * 4, 256) + gp_align_up(T * 4, 256));
     if (!acc) GP_FAIL("allocator returned NULL for TEMP");
     uint32_t* order_bwd = (uint32_t*)((char*)acc + gp_align_up(acc_floats * 4, 256));
-    if (R > 0) {        // (tile order for the composite backward + the accumulators' fill, one launch)
+    if (prepared) {            // (both done inside the loss launch)
+    } else if (R > 0) {        // (tile order for the composite backward + the accumulators' fill, one launch)
         const unsigned zb = (unsigned)std::min<size_t>(2048, std::max<size_t>(1, (acc_floats / 4 + 1023) / 1024));
         hipLaunchKernelGGL(gp_bwd_prologue_kernel, dim3(1 + zb), dim3(1024), 0, s, il.ranges, il.tile_work, (int)T, order_bwd, acc, acc_floats);
         GP_LAUNCH_CHECK();

@@ -1,6 +1,7 @@
-// loss_adam_kernels.h -- the multi-tensor Adam launch's table and chunk body (shared by gp_adam_multi_kernel and by the launch that
-// carries the same chunks beside the keypoint MLP's data backward, deform_mlp_small.hip), and the "rider" slot through which
-// gp_train_step_run hands that launch an optimizer table.  Everything else of loss_adam_kernels.hip is private to it.
+// loss_adam_kernels.h -- the multi-tensor Adam launch's table and chunk body (shared by gp_adam_multi_kernel and by the launches that
+// carry the same chunks: the keypoint MLP's data backward, deform_mlp_small.hip, and the keypoint blend's backward, deform_kernels.hip),
+// the loss finalize's body (the blend backward's launch carries it too), and the "rider" slots through which gp_train_step_run hands
+// those launches their passengers.  Everything else of loss_adam_kernels.hip is private to it.
 #pragma once
 #include "gp_common.h"
 
@@ -90,3 +91,122 @@ int gp_adam_rider_arm(int count, float* const* params, float* const* grads, floa
                       const int64_t* numels, const float* lrs, const int64_t* steps, float beta1, float beta2, float eps, int zero_grad,
                       uint32_t keep_grad_mask, const uint32_t* skip_flag);
 int gp_adam_rider_flush(hipStream_t s);     // launches an armed rider as a plain gp_adam_multi_kernel and disarms the slot
+
+// ---- the loss scalar: loss = (1-lam) * sums[0]/n + lam * (1 - sums[1]/n) [+ scale/n * sum|x|], one 256-thread workgroup
+__device__ __forceinline__ float block_sum_256(float v, float* s_red) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) s_red[wave] = v;
+    __syncthreads();
+    return s_red[0] + s_red[1] + s_red[2] + s_red[3];
+}
+// The slot totals in a fixed order: thread k walks slots k, k + 256, ..., xor-butterfly inside the wave, the four wave sums
+// through LDS.  (Round 2 let ONE thread walk the slots: 512 dependent double loads, 19 us for a scalar.)
+__device__ __forceinline__ void loss_slot_totals(const double* __restrict__ sums, int nslots, double* s_red /*[8]*/, double& s0, double& s1) {
+    const int tid = threadIdx.x;
+    double a = 0.0, b = 0.0;
+    // eight slot pairs per trip to memory, added in the same order as one by one (as a rolled loop every pair was a dependent
+    // round trip: 16 + 8 of them made this scalar's kernel 9.5 us between the loss forward and its backward)
+    const double2* s2 = reinterpret_cast<const double2*>(sums);
+    for (int k0 = tid; k0 < nslots; k0 += 256 * 8) {
+        double2 v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) { const int k = k0 + 256 * u; v[u] = s2[k < nslots ? k : nslots - 1]; }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) if (k0 + 256 * u < nslots) { a += v[u].x; b += v[u].y; }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        a += __shfl_xor(a, d);
+        b += __shfl_xor(b, d);
+    }
+    if ((tid & 63) == 0) { s_red[2 * (tid >> 6)] = a; s_red[2 * (tid >> 6) + 1] = b; }
+    __syncthreads();
+    s0 = (s_red[0] + s_red[2]) + (s_red[4] + s_red[6]);
+    s1 = (s_red[1] + s_red[3]) + (s_red[5] + s_red[7]);
+}
+struct LossFinalizeDev {
+    const double* sums;         // [nslots][2]: the loss kernel's per-tile sums
+    int nslots;
+    double n;                   // channels * H * W
+    float lambda;
+    const float* x;             // the regulariser's input (NULL: no regulariser term)
+    long nx;
+    float scale_over_n;
+    float* loss;
+};
+// (fixed summation order: the same scalar whichever launch carries the workgroup)
+__device__ __forceinline__ void loss_finalize_body(const LossFinalizeDev& f, float* s_red /*[4]*/, double* s_tot /*[8]*/) {
+    float tot = 0.f;
+    if (f.x) {
+        const float* __restrict__ x = f.x;
+        const long nx = f.nx;
+        float acc = 0.f;
+        if ((nx & 3) == 0 && (((uintptr_t)x) & 15) == 0) {          // 16-byte loads, four independent per thread in flight
+            const float4* x4 = (const float4*)x;
+            const long n4 = nx >> 2;
+            for (long i0 = threadIdx.x; i0 < n4; i0 += 256 * 8) {
+                float4 v[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) { const long i = i0 + 256 * u; v[u] = x4[i < n4 ? i : n4 - 1]; }
+#pragma unroll
+                for (int u = 0; u < 8; ++u)
+                    if (i0 + 256 * u < n4) acc += (fabsf(v[u].x) + fabsf(v[u].y)) + (fabsf(v[u].z) + fabsf(v[u].w));
+            }
+        } else {
+            for (long i = threadIdx.x; i < nx; i += 256) acc += fabsf(x[i]);
+        }
+        tot = block_sum_256(acc, s_red);
+    }
+    double s0, s1;
+    loss_slot_totals(f.sums, f.nslots, s_tot, s0, s1);
+    if (threadIdx.x == 0) {
+        const float l = (float)((1.0 - (double)f.lambda) * s0 / f.n + (double)f.lambda * (1.0 - s1 / f.n));
+        f.loss[0] = f.x ? l + tot * f.scale_over_n : l;
+    }
+}
+
+// ---- riders of the keypoint blend's backward launch (gp_blend_backward, nn = 6 / 8 kernels; deform_kernels.hip).  That launch is bound
+// by its own instruction stream and leaves HBM half idle; gp_train_step_run puts into it, as workgroups IN FRONT of the blend's own:
+//   * the loss finalize (one workgroup): nothing on the device reads the scalar, and the launch runs before every optimizer launch
+//     that moves the regulariser's input;
+//   * the Adam chunks of the tensors whose gradients the projection backward has already finished (_scaling, _opacity).
+// Armed by gp_train_step_run only, consumed by gp_blend_backward (which clears the flags of what it carried); whatever is still armed
+// afterwards is launched on its own (gp_blend_rider_flush).  One slot per host thread.
+struct BlendRideDev {
+    AdamTable t;
+    float b1, b2, eps;
+    int zero_grad;
+    const uint32_t* skip_flag;
+    unsigned adam_chunks;       // workgroups [fin_blocks, fin_blocks + adam_chunks): one Adam chunk each
+    unsigned fin_blocks;        // 0 / 1: workgroup 0 is the loss finalize
+    LossFinalizeDev fin;
+};
+struct GpBlendRider {
+    GpAdamRider adam;
+    LossFinalizeDev fin;
+    bool fin_armed;
+};
+GpBlendRider* gp_blend_rider_slot();
+int gp_blend_rider_arm_adam(int count, float* const* params, float* const* grads, float* const* exp_avgs, float* const* exp_avg_sqs,
+                            const int64_t* numels, const float* lrs, const int64_t* steps, float beta1, float beta2, float eps,
+                            int zero_grad, uint32_t keep_grad_mask, const uint32_t* skip_flag);
+int gp_blend_rider_arm_finalize(const double* sums, int32_t channels, int32_t H, int32_t W, float lambda_dssim, const float* x, int64_t n,
+                                float scale, float* loss);
+int gp_blend_rider_flush(hipStream_t s);    // launches what is still armed on its own and disarms the slot
+void gp_blend_rider_disarm();
+
+// ---- rider of the fused loss launch (gp_loss_l1_ssim_fused): the composite backward's prologue -- its tile order (needs the composite
+// FORWARD's ranges and tile_work only) and the zero fill of its accumulators (needs nothing).  gp_train_step_run obtains the block
+// from gp_raster_backward_prepare (gp_capi_raster.hip) and arms the slot; the next gp_loss_l1_ssim_fused call consumes it.
+struct GpLossPrologue {
+    const int2* ranges;
+    const int32_t* tile_work;
+    int T;
+    uint32_t* order;
+    float* acc;
+    size_t acc_floats;
+    bool armed;
+};
+GpLossPrologue* gp_loss_prologue_slot();

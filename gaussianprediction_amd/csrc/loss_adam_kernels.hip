@@ -9,7 +9,9 @@
 //     gradient it consumed (the flat gradient bucket is reused by the next step).
 #include "gp_common.h"
 #include "loss_adam_kernels.h"
+#include "raster_kernels.h"      // gp_tile_order_body256
 
+#define GP_LOSS_REG_MAX 65536
 #define LT 32              // output tile edge
 #define LH 5               // window half width
 #define LE (LT + 2 * LH)   // staged tile edge (42)
@@ -17,15 +19,6 @@
 #define LHP (LT + 1)       // padded row of the horizontally filtered maps
 
 struct Win11 { float w[11]; };
-
-__device__ __forceinline__ float block_sum_256(float v, float* s_red) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) s_red[wave] = v;
-    __syncthreads();
-    return s_red[0] + s_red[1] + s_red[2] + s_red[3];
-}
 
 // forward: sums[0] += sum |a-b| ; sums[1] += sum ssim_map ; optional derivative maps
 // dmap[0] = d ssim / d conv(a), dmap[1] = d ssim / d conv(a^2), dmap[2] = d ssim / d conv(a b)
@@ -251,7 +244,7 @@ __global__ __launch_bounds__(256) void gp_l1_ssim_fused_kernel(const float* __re
                                                               Win11 win, float lambda, const float* __restrict__ upstream,
                                                               double* __restrict__ sums, float* __restrict__ dimg,
                                                               const float* __restrict__ reg_x, long reg_n, float reg_scale_over_n,
-                                                              float* __restrict__ reg_g) {
+                                                              float* __restrict__ reg_g, GpLossPrologue pro) {
     // The two maps of a filter round live INTERLEAVED in LDS (one 8-byte read = the operand pair of a packed operation; as two planes
     // every pair cost two reads and two register moves: a quarter of the kernel's instructions).
     typedef float f2 __attribute__((ext_vector_type(2)));
@@ -264,8 +257,27 @@ __global__ __launch_bounds__(256) void gp_l1_ssim_fused_kernel(const float* __re
     float (*s_g2)[LHP] = (float (*)[LHP])((float*)&s_h[0][0] + 2 * LE * LHP);
     static_assert(3 * LE * LP <= 2 * LF * LFP && 3 * LE * LHP <= 2 * LF * LP, "aliased planes must fit");
     const int tid = threadIdx.x;
-    const int tx0 = blockIdx.x * LT, ty0 = blockIdx.y * LT, ch = blockIdx.z;
-    if (reg_g && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0) {   // the regulariser's gradient rides along (see the backward kernel)
+    // The grid is LINEAR (workgroups are dispatched in blockIdx.x order): with a prologue on board (pro.order, gp_train_step_run) workgroup 0
+    // orders the composite backward's tiles -- a ~9 us chain of dependent steps that must start first, not behind the last tile -- and
+    // workgroup b > 0 is loss tile b - 1.  Its 1 KB of counters and the tiles' buckets live in the filter planes (the ordering workgroup
+    // filters nothing): the kernel's LDS, hence four workgroups per CU, stays what it was.
+    const unsigned first = pro.order ? 1u : 0u;
+    if (first && blockIdx.x == 0) {
+        gp_tile_order_body256(pro.ranges, pro.tile_work, pro.T, pro.order, (uint32_t*)&s_h[0][0], (uint32_t*)&s_h[0][0] + 128,
+                              (uint8_t*)&s_ab[0][0], (int)sizeof(s_ab));
+        return;
+    }
+    const unsigned lb = blockIdx.x - first;         // = x + gx * (y + gy * channel): also the slot of `sums`
+    const unsigned ngx = (unsigned)(W + LT - 1) / LT, ngy = (unsigned)(H + LT - 1) / LT;
+    const unsigned ch = lb / (ngx * ngy), lrem = lb - ch * (ngx * ngy), lby = lrem / ngx, lbx = lrem - lby * ngx;
+    const int tx0 = (int)lbx * LT, ty0 = (int)lby * LT;
+    if (pro.acc) {      // the composite backward's accumulators, zeroed by all loss workgroups: fire-and-forget stores under the filter arithmetic
+        const size_t n4 = pro.acc_floats >> 2, stride = (size_t)(gridDim.x - first) * 256;
+        float4* a4 = reinterpret_cast<float4*>(pro.acc);
+        for (size_t i = (size_t)lb * 256 + tid; i < n4; i += stride) a4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (lb == 0 && (unsigned)tid < (unsigned)(pro.acc_floats & 3)) pro.acc[(n4 << 2) + tid] = 0.f;
+    }
+    if (reg_g && lb == 0) {   // the regulariser's gradient rides along (see the backward kernel)
         const float c = (upstream ? upstream[0] : 1.f) * reg_scale_over_n;
         for (long i = tid; i < reg_n; i += 256) { const float v = reg_x[i]; reg_g[i] = v > 0.f ? c : (v < 0.f ? -c : 0.f); }
     }
@@ -422,9 +434,8 @@ __global__ __launch_bounds__(256) void gp_l1_ssim_fused_kernel(const float* __re
     __syncthreads();
     const float ss_tot = block_sum_256(ss, s_red);
     if (tid == 0) {
-        const unsigned slot = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-        sums[2 * slot] = (double)l1_tot;
-        sums[2 * slot + 1] = (double)ss_tot;
+        sums[2 * lb] = (double)l1_tot;
+        sums[2 * lb + 1] = (double)ss_tot;
     }
 }
 
@@ -466,66 +477,17 @@ __global__ __launch_bounds__(256) void gp_adam_multi_kernel(AdamTable t, float b
     adam_chunk_body<256>(t, blockIdx.x, threadIdx.x, b1, b2, eps, zero_grad, skip_flag);
 }
 
-// The slot totals in a fixed order: thread k walks slots k, k + 256, ..., xor-butterfly inside the wave, the four wave sums
-// through LDS.  (Round 2 let ONE thread walk the slots: 512 dependent double loads, 19 us for a scalar.)
-__device__ __forceinline__ void loss_slot_totals(const double* __restrict__ sums, int nslots, double* s_red /*[8]*/, double& s0, double& s1) {
-    const int tid = threadIdx.x;
-    double a = 0.0, b = 0.0;
-    // eight slot pairs per trip to memory, added in the same order as one by one (as a rolled loop every pair was a dependent
-    // round trip: 16 + 8 of them made this scalar's kernel 9.5 us between the loss forward and its backward)
-    const double2* s2 = reinterpret_cast<const double2*>(sums);
-    for (int k0 = tid; k0 < nslots; k0 += 256 * 8) {
-        double2 v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) { const int k = k0 + 256 * u; v[u] = s2[k < nslots ? k : nslots - 1]; }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) if (k0 + 256 * u < nslots) { a += v[u].x; b += v[u].y; }
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        a += __shfl_xor(a, d);
-        b += __shfl_xor(b, d);
-    }
-    if ((tid & 63) == 0) { s_red[2 * (tid >> 6)] = a; s_red[2 * (tid >> 6) + 1] = b; }
-    __syncthreads();
-    s0 = (s_red[0] + s_red[2]) + (s_red[4] + s_red[6]);
-    s1 = (s_red[1] + s_red[3]) + (s_red[5] + s_red[7]);
-}
-
-// loss = (1-lam) * sums[0]/n + lam * (1 - sums[1]/n)   (keeps the scalar on the device)
+// loss = (1-lam) * sums[0]/n + lam * (1 - sums[1]/n) [+ scale/n * sum|x|]  (keeps the scalar on the device; one workgroup, fixed
+// summation order: loss_finalize_body, loss_adam_kernels.h)
 __global__ __launch_bounds__(256) void gp_loss_finalize_kernel(const double* __restrict__ sums, int nslots, double n, float lambda, float* __restrict__ loss) {
-    __shared__ double s_tot[8];
-    double s0, s1;
-    loss_slot_totals(sums, nslots, s_tot, s0, s1);
-    if (threadIdx.x == 0) loss[0] = (float)((1.0 - (double)lambda) * s0 / n + (double)lambda * (1.0 - s1 / n));
-}
-
-// the same + scale/n * sum|x| (one workgroup; fixed summation order)
-__global__ __launch_bounds__(256) void gp_loss_finalize_reg_kernel(const double* __restrict__ sums, int nslots, double n, float lambda,
-                                                                  const float* __restrict__ x, long nx, float scale_over_n,
-                                                                  float* __restrict__ loss) {
     __shared__ float s_red[4];
     __shared__ double s_tot[8];
-    float acc = 0.f;
-    if ((nx & 3) == 0 && (((uintptr_t)x) & 15) == 0) {          // 16-byte loads, four independent per thread in flight
-        const float4* x4 = (const float4*)x;
-        const long n4 = nx >> 2;
-        for (long i0 = threadIdx.x; i0 < n4; i0 += 256 * 8) {
-            float4 v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) { const long i = i0 + 256 * u; v[u] = x4[i < n4 ? i : n4 - 1]; }
-#pragma unroll
-            for (int u = 0; u < 8; ++u)
-                if (i0 + 256 * u < n4) acc += (fabsf(v[u].x) + fabsf(v[u].y)) + (fabsf(v[u].z) + fabsf(v[u].w));
-        }
-    } else {
-        for (long i = threadIdx.x; i < nx; i += 256) acc += fabsf(x[i]);
-    }
-    const float tot = block_sum_256(acc, s_red);
-    double s0, s1;
-    loss_slot_totals(sums, nslots, s_tot, s0, s1);
-    if (threadIdx.x == 0)
-        loss[0] = (float)((1.0 - (double)lambda) * s0 / n + (double)lambda * (1.0 - s1 / n)) + tot * scale_over_n;
+    loss_finalize_body(LossFinalizeDev{sums, nslots, n, lambda, nullptr, 0L, 0.f, loss}, s_red, s_tot);
+}
+__global__ __launch_bounds__(256) void gp_loss_finalize_reg_kernel(LossFinalizeDev f) {
+    __shared__ float s_red[4];
+    __shared__ double s_tot[8];
+    loss_finalize_body(f, s_red, s_tot);
 }
 
 // out[0] = base[0] + scale * mean|x|   [REF scene/gaussian_model.py:174-178: 1e-5 * mean(|motion feature|)]
@@ -598,27 +560,31 @@ extern "C" int gp_loss_l1_ssim_fused(const float* img, const float* gt, int32_t 
                                      const float* upstream, double* sums, float* dimg, const float* x, int64_t n, float scale, float* gx,
                                      gp_stream_t stream_) {
     hipStream_t s = (hipStream_t)stream_;
+    // the composite backward's prologue, if gp_train_step_run left one for this launch (consumed or dropped here, whatever happens)
+    GpLossPrologue pro = *gp_loss_prologue_slot();
+    gp_loss_prologue_slot()->armed = false;
+    if (!pro.armed) memset(&pro, 0, sizeof(pro));
     if (!img || !gt || !sums || !dimg) GP_FAIL("null argument");
     if (channels != 3 || H <= 0 || W <= 0) GP_FAIL("expects a [3,H,W] image (got C=%d H=%d W=%d)", channels, H, W);
     if ((x != nullptr) != (gx != nullptr)) GP_FAIL("regulariser input and gradient must be given together");
     if (x && (n <= 0 || n > 65536)) GP_FAIL("regulariser input must have 1..65536 elements");
     GpProfScope _p("l1_ssim_fused", s);
-    hipLaunchKernelGGL(gp_l1_ssim_fused_kernel, dim3((W + LT - 1) / LT, (H + LT - 1) / LT, 3), dim3(256), 0, s, img, gt, H, W, make_window(),
-                       lambda_dssim, upstream, sums, dimg, x, x ? (long)n : 0L, x ? scale / (float)n : 0.f, gx);
+    const unsigned tiles = (unsigned)((W + LT - 1) / LT) * (unsigned)((H + LT - 1) / LT) * 3u;
+    hipLaunchKernelGGL(gp_l1_ssim_fused_kernel, dim3(tiles + (pro.order ? 1u : 0u)), dim3(256), 0, s, img, gt, H, W, make_window(),
+                       lambda_dssim, upstream, sums, dimg, x, x ? (long)n : 0L, x ? scale / (float)n : 0.f, gx, pro);
     GP_LAUNCH_CHECK();
     return 0;
 }
 
 // the two calls above with the regulariser  scale * mean|x|  [REF scene/gaussian_model.py:174-178] folded in (x small: the
 // keypoint features of stage 2/3) -- saves the regulariser's own forward and backward launches
-#define GP_LOSS_REG_MAX 65536
 extern "C" int gp_loss_l1_ssim_finalize_reg(const double* sums, int32_t channels, int32_t H, int32_t W, float lambda_dssim,
                                             const float* x, int64_t n, float scale, float* loss, gp_stream_t stream_) {
     if (!sums || !loss || !x) GP_FAIL("null argument");
     if (((uintptr_t)sums & 15) != 0) GP_FAIL("sums must be 16-byte aligned");
     if (n <= 0 || n > GP_LOSS_REG_MAX) GP_FAIL("regulariser input must have 1..%d elements (use gp_l1_mean_forward beyond)", GP_LOSS_REG_MAX);
-    hipLaunchKernelGGL(gp_loss_finalize_reg_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream_, sums, (int)GP_LOSS_SUM_SLOTS(H, W), (double)channels * H * W, lambda_dssim,
-                       x, (long)n, scale / (float)n, loss);
+    LossFinalizeDev f = {sums, (int)GP_LOSS_SUM_SLOTS(H, W), (double)channels * H * W, lambda_dssim, x, (long)n, scale / (float)n, loss};
+    hipLaunchKernelGGL(gp_loss_finalize_reg_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream_, f);
     GP_LAUNCH_CHECK();
     return 0;
 }
@@ -724,6 +690,60 @@ int gp_adam_rider_flush(hipStream_t s) {
     hipLaunchKernelGGL(gp_adam_multi_kernel, dim3(r->chunks), dim3(256), 0, s, r->t, r->b1, r->b2, r->eps, r->zero_grad, r->skip_flag);
     GP_LAUNCH_CHECK();
     return 0;
+}
+
+// ---- the riders of the blend backward's launch and of the fused loss launch (loss_adam_kernels.h)
+GpBlendRider* gp_blend_rider_slot() {
+    static thread_local GpBlendRider slot = {};
+    return &slot;
+}
+void gp_blend_rider_disarm() {
+    GpBlendRider* r = gp_blend_rider_slot();
+    r->adam.armed = false;
+    r->fin_armed = false;
+}
+int gp_blend_rider_arm_adam(int count, float* const* params, float* const* grads, float* const* exp_avgs, float* const* exp_avg_sqs,
+                            const int64_t* numels, const float* lrs, const int64_t* steps, float beta1, float beta2, float eps,
+                            int zero_grad, uint32_t keep_grad_mask, const uint32_t* skip_flag) {
+    GpAdamRider* r = &gp_blend_rider_slot()->adam;
+    r->armed = false;
+    long chunks = 0;
+    if (adam_build_table(r->t, chunks, count, params, grads, exp_avgs, exp_avg_sqs, numels, lrs, steps, beta1, beta2, keep_grad_mask)) return 1;
+    r->b1 = beta1; r->b2 = beta2; r->eps = eps; r->zero_grad = zero_grad; r->skip_flag = skip_flag; r->chunks = (unsigned)chunks;
+    r->armed = chunks > 0;
+    return 0;
+}
+int gp_blend_rider_arm_finalize(const double* sums, int32_t channels, int32_t H, int32_t W, float lambda_dssim, const float* x, int64_t n,
+                                float scale, float* loss) {
+    GpBlendRider* r = gp_blend_rider_slot();
+    r->fin_armed = false;
+    if (!sums || !loss) GP_FAIL("null argument");
+    if (((uintptr_t)sums & 15) != 0) GP_FAIL("sums must be 16-byte aligned");
+    if (x && (n <= 0 || n > GP_LOSS_REG_MAX)) GP_FAIL("regulariser input must have 1..%d elements", GP_LOSS_REG_MAX);
+    r->fin = LossFinalizeDev{sums, (int)GP_LOSS_SUM_SLOTS(H, W), (double)channels * H * W, lambda_dssim, x, x ? (long)n : 0L,
+                             x ? scale / (float)n : 0.f, loss};
+    r->fin_armed = true;
+    return 0;
+}
+int gp_blend_rider_flush(hipStream_t s) {
+    GpBlendRider* r = gp_blend_rider_slot();
+    const bool fin = r->fin_armed, adam = r->adam.armed;
+    gp_blend_rider_disarm();
+    if (fin) {
+        hipLaunchKernelGGL(gp_loss_finalize_reg_kernel, dim3(1), dim3(256), 0, s, r->fin);
+        GP_LAUNCH_CHECK();
+    }
+    if (adam) {
+        GpProfScope _p("adam", s);
+        hipLaunchKernelGGL(gp_adam_multi_kernel, dim3(r->adam.chunks), dim3(256), 0, s, r->adam.t, r->adam.b1, r->adam.b2, r->adam.eps,
+                           r->adam.zero_grad, r->adam.skip_flag);
+        GP_LAUNCH_CHECK();
+    }
+    return 0;
+}
+GpLossPrologue* gp_loss_prologue_slot() {
+    static thread_local GpLossPrologue slot = {};
+    return &slot;
 }
 
 extern "C" int gp_adam_step_multi(int32_t count, float* const* params, float* const* grads, float* const* exp_avgs,

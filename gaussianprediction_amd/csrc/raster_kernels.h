@@ -98,6 +98,47 @@ __device__ __forceinline__ int gp_tile_bucket(int w) {
     const int v = lg * 4 + sub;
     return 126 - (v < 126 ? v : 126);
 }
+// gp_tile_order_body (raster_kernels.hip) for a 256-thread workgroup that rides in another kernel's launch (the fused loss carries
+// the composite backward's ordering): same buckets, same counting sort -- the order inside a bucket only affects scheduling.  The
+// tiles come in batches of 16 per thread (every load of a batch in flight together); their buckets wait in the carrier's LDS
+// (s_bk, bk_cap bytes; a larger T reads the ranges a second time).  s_cnt / s_base: 128 words each.
+__device__ __forceinline__ void gp_tile_order_body256(const int2* __restrict__ ranges, const int32_t* __restrict__ work_hint, int T,
+                                                      uint32_t* __restrict__ order, uint32_t* s_cnt, uint32_t* s_base, uint8_t* s_bk,
+                                                      int bk_cap) {
+    constexpr int PER = 16;
+    const int tid = threadIdx.x;
+    const bool keep = T <= bk_cap;
+    auto bucket_of = [&](int t) { const int2 r = ranges[t]; int w = r.y - r.x; if (work_hint) w = min(w, work_hint[t]); return gp_tile_bucket(w); };
+    if (tid < 128) s_cnt[tid] = 0;
+    __syncthreads();
+    for (int t0 = 0; t0 < T; t0 += 256 * PER) {
+        int2 rg[PER];
+        int wh[PER];
+#pragma unroll
+        for (int r = 0; r < PER; ++r) {
+            const int t = t0 + r * 256 + tid;
+            rg[r] = ranges[t < T ? t : T - 1];
+            wh[r] = work_hint ? work_hint[t < T ? t : T - 1] : 0x7fffffff;
+        }
+#pragma unroll
+        for (int r = 0; r < PER; ++r) {
+            const int t = t0 + r * 256 + tid;
+            if (t >= T) continue;
+            const int b = gp_tile_bucket(min(rg[r].y - rg[r].x, wh[r]));
+            if (keep) s_bk[t] = (uint8_t)b;
+            atomicAdd(&s_cnt[b], 1u);
+        }
+    }
+    __syncthreads();
+    if (tid < 128) {
+        uint32_t run = 0;
+#pragma unroll 16
+        for (int b = 0; b < 128; ++b) { const uint32_t c = s_cnt[b]; run += b < tid ? c : 0u; }
+        s_base[tid] = run;
+    }
+    __syncthreads();
+    for (int t = tid; t < T; t += 256) order[atomicAdd(&s_base[keep ? (int)s_bk[t] : bucket_of(t)], 1u)] = (uint32_t)t;
+}
 int gp_pair_counters_read(unsigned long long* out4);
 int gp_bwd_set_ablate(int v);
 __global__ __launch_bounds__(256) void gp_composite_fwd_count_kernel(RasterDims d, const int2* __restrict__ ranges,
