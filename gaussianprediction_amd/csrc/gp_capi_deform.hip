@@ -135,9 +135,8 @@ extern "C" int gp_mlp_forward(const gp_mlp_params* p, const gp_mlp_input* x, flo
 }
 
 // Internal (gp_train_step_run): would gp_mlp_backward take the feature-split data kernel for these arguments?  Only that kernel honours
-// a request to ADD the input-feature gradient into dL_dfeature (gp_mlp_backward_accumulate_dfeature_once: the keypoint features also take
+// a request to ADD the input-feature gradient into dL_dfeature (gp_mlp_backward_impl's accumulate_dfeature: the keypoint features also take
 // the regulariser's gradient, which the loss kernel has already written there -- one launch less per step than "=" into a temporary + add).
-static thread_local int g_dfeature_accumulate = 0;
 bool gp_mlp_backward_splits(const gp_mlp_params* p, int64_t rows) {
     if (!p) return false;
     MlpDev m;
@@ -147,13 +146,12 @@ bool gp_mlp_backward_splits(const gp_mlp_params* p, int64_t rows) {
     int* st = nullptr;
     return mlp_split_grid(m, p->scratch, mode, st) != 0 && (mode == 1 || mode == 3);
 }
-void gp_mlp_backward_accumulate_dfeature_once() { g_dfeature_accumulate = 1; }
 
-extern "C" int gp_mlp_backward(const gp_mlp_params* p, const gp_mlp_input* x, const float* acts, const float* dL_dout,
-                               gp_mlp_grads* g, float* dL_dfeature, float* dL_dxyz, gp_alloc_fn alloc, void* alloc_ctx,
-                               gp_stream_t stream_) {
+// `rider` (gp_train_step_run; NULL or not armed: none): an optimizer launch whose chunks the small-row data kernel's launch carries
+int gp_mlp_backward_impl(const gp_mlp_params* p, const gp_mlp_input* x, const float* acts, const float* dL_dout, gp_mlp_grads* g,
+                         float* dL_dfeature, float* dL_dxyz, gp_alloc_fn alloc, void* alloc_ctx, gp_stream_t stream_, GpAdamRider* rider,
+                         bool accumulate_dfeature) {
     hipStream_t s = (hipStream_t)stream_;
-    struct ClearAcc { ~ClearAcc() { g_dfeature_accumulate = 0; } } clear_acc;      // (a "+=" request is for THIS call, however it returns)
     MlpDev m;
     if (make_mlp(p, x, m)) return 1;
     if (m.rows == 0) return 0;
@@ -165,7 +163,6 @@ extern "C" int gp_mlp_backward(const gp_mlp_params* p, const gp_mlp_input* x, co
     const size_t dz_bytes = gp_align_up((size_t)4 * m.rows * 256 * sizeof(float), 256);
     float* dz = (float*)alloc(alloc_ctx, GP_BUF_TEMP, dz_bytes);
     if (!dz) GP_FAIL("allocator returned NULL for TEMP (%zu B)", dz_bytes);
-    GpAdamRider* rider = gp_adam_rider_slot();
     int split_mode = 0;
     int* split_state = nullptr;
     // the feature-split form (deform_mlp_small.hip) once a forward has validated its XCD-local exchange on this device (mode 1), or in
@@ -175,15 +172,13 @@ extern "C" int gp_mlp_backward(const gp_mlp_params* p, const gp_mlp_input* x, co
         float* gx = (float*)((char*)p->scratch + GP_MLP_SCRATCH_FLAG_BYTES);
         uint32_t* flags = (uint32_t*)p->scratch;
         // (an armed rider stays armed: beside this latency-chained kernel the optimizer's stream costs more than it hides -- it is
-        // launched behind the MLP backward by its owner, gp_adam_rider_flush)
+        // launched behind the MLP backward by its owner)
         GpProfScope _p("mlp_bwd_data", s);
-        const int acc = g_dfeature_accumulate;
-        g_dfeature_accumulate = 0;
         hipLaunchKernelGGL(gp_mlp_bwd_data_split_small_kernel, dim3(split), dim3(256), 0, s, m, sh, dL_dout, dz, dL_dfeature, dL_dxyz, gx, flags,
-                           flags + GP_MLP_SCRATCH_ERR_WORD, (split_mode == 3 ? 1 : 0) | (acc ? 2 : 0));
+                           flags + GP_MLP_SCRATCH_ERR_WORD, (split_mode == 3 ? 1 : 0) | (accumulate_dfeature ? 2 : 0));
         GP_LAUNCH_CHECK();
-    } else if (m.rows <= GP_MLP_SMALL_ROWS && rider->armed) {
-        // gp_train_step_run left an optimizer launch that needs nothing of this backward: its chunks ride in the data kernel's launch
+    } else if (m.rows <= GP_MLP_SMALL_ROWS && rider && rider->armed) {
+        // gp_train_step_run passed an optimizer launch that needs nothing of this backward: its chunks ride in the data kernel's launch
         // (deform_mlp_small.hip).  The scope carries the optimizer's name: its bytes are what the launch moves.
         rider->armed = false;
         const unsigned n_mlp = gp_blocks((size_t)m.rows, 16);
@@ -256,6 +251,11 @@ extern "C" int gp_mlp_backward(const gp_mlp_params* p, const gp_mlp_input* x, co
     }
     return 0;
 }
+extern "C" int gp_mlp_backward(const gp_mlp_params* p, const gp_mlp_input* x, const float* acts, const float* dL_dout,
+                               gp_mlp_grads* g, float* dL_dfeature, float* dL_dxyz, gp_alloc_fn alloc, void* alloc_ctx,
+                               gp_stream_t stream_) {
+    return gp_mlp_backward_impl(p, x, acts, dL_dout, g, dL_dfeature, dL_dxyz, alloc, alloc_ctx, stream_, nullptr, false);
+}
 
 static int make_blend(const gp_blend_args* a, BlendDev& b) {
     if (!a) GP_FAIL("null blend args");
@@ -286,19 +286,18 @@ extern "C" int gp_blend_forward(const gp_blend_args* a, float* xyz_t, float* q_t
     return 0;
 }
 
-extern "C" int gp_blend_backward(const gp_blend_args* a, const float* dL_dxyz_t, const float* dL_dq_t, float* dL_ddelta,
-                                 float* dL_draw_w, float* dL_dxyz, float* dL_drot, gp_alloc_fn alloc, void* alloc_ctx,
-                                 gp_stream_t stream_) {
+// `rider` (gp_train_step_run; NULL: none): the loss finalize and / or Adam chunks that travel in front of the blend's workgroups
+int gp_blend_backward_impl(const gp_blend_args* a, const float* dL_dxyz_t, const float* dL_dq_t, float* dL_ddelta, float* dL_draw_w,
+                           float* dL_dxyz, float* dL_drot, gp_alloc_fn alloc, void* alloc_ctx, gp_stream_t stream_, GpBlendRider* rider) {
     BlendDev b;
     if (make_blend(a, b)) return 1;
     if (b.N == 0) return 0;
     if (!dL_dxyz_t || !dL_dq_t || !dL_ddelta || !dL_dxyz || !dL_drot) GP_FAIL("null argument");     // dL_draw_w may be NULL
     const bool al = (((uintptr_t)b.raw_w | (uintptr_t)b.knn | (uintptr_t)dL_draw_w) & 15) == 0;
     const bool i16 = b.knn16 != nullptr;
-    // riders of the fused step (loss_adam_kernels.h, GpBlendRider; armed by gp_train_step_run only): the nn = 6 / 8 kernels carry them,
-    // what this call does not carry stays armed for gp_blend_rider_flush
-    GpBlendRider* rider = gp_blend_rider_slot();
-    const bool ride = (rider->fin_armed || rider->adam.armed) && al && (b.nn == 6 || b.nn == 8);
+    // riders of the fused step (loss_adam_kernels.h, GpBlendRider): the nn = 6 / 8 kernels carry them, what this call does not carry
+    // stays armed for the caller to launch
+    const bool ride = rider && (rider->fin_armed || rider->adam.armed) && al && (b.nn == 6 || b.nn == 8);
     const unsigned adam_chunks = ride && rider->adam.armed ? rider->adam.chunks : 0u;
     unsigned blocks = gp_blocks((size_t)b.N, 256);
     // persistent: four workgroups per CU (LDS), their partials are summed by the reduce kernel.  Beside Adam chunks THREE per CU: the
@@ -325,7 +324,7 @@ extern "C" int gp_blend_backward(const gp_blend_args* a, const float* dL_dxyz_t,
             r.skip_flag = rider->adam.skip_flag; r.adam_chunks = adam_chunks;
         }
         if (rider->fin_armed) { r.fin = rider->fin; r.fin_blocks = 1; }
-        gp_blend_rider_disarm();
+        rider->adam.armed = rider->fin_armed = false;
         hipLaunchKernelGGL(b.nn == 6 ? (i16 ? gp_blend_bwd6_i16_ride_kernel : gp_blend_bwd6_ride_kernel)
                                      : (i16 ? gp_blend_bwd8_i16_ride_kernel : gp_blend_bwd8_ride_kernel),
                            dim3(r.fin_blocks + r.adam_chunks + blocks), dim3(256), lds, (hipStream_t)stream_, r, b, dL_dxyz_t, dL_dq_t, dL_ddelta,
@@ -343,6 +342,11 @@ extern "C" int gp_blend_backward(const gp_blend_args* a, const float* dL_dxyz_t,
         GP_LAUNCH_CHECK();
     } }
     return 0;
+}
+extern "C" int gp_blend_backward(const gp_blend_args* a, const float* dL_dxyz_t, const float* dL_dq_t, float* dL_ddelta,
+                                 float* dL_draw_w, float* dL_dxyz, float* dL_drot, gp_alloc_fn alloc, void* alloc_ctx,
+                                 gp_stream_t stream_) {
+    return gp_blend_backward_impl(a, dL_dxyz_t, dL_dq_t, dL_ddelta, dL_draw_w, dL_dxyz, dL_drot, alloc, alloc_ctx, stream_, nullptr);
 }
 
 extern "C" int gp_activations_forward(int64_t n, const float* scaling_raw, const float* opacity_raw, const float* delta_o,

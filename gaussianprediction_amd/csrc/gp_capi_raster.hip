@@ -297,22 +297,10 @@ extern "C" int gp_raster_forward(const gp_raster_settings* st, const gp_raster_i
 }
 
 // The backward's TEMP block (accumulators + tile order) handed out BEFORE the backward: gp_train_step_run lets the fused loss launch carry
-// the prologue (loss_adam_kernels.h, GpLossPrologue), and the gp_raster_backward call for the same saved state finds the block here.
-struct GpBwdPrepared {
-    const void* image;      // saved->image of the forward the block belongs to
-    float* acc;
-    size_t acc_floats;
-    bool armed;
-};
-static GpBwdPrepared* bwd_prepared_slot() {
-    static thread_local GpBwdPrepared slot = {};
-    return &slot;
-}
-void gp_raster_backward_unprepare() { bwd_prepared_slot()->armed = false; }
+// the prologue (loss_adam_kernels.h, GpLossPrologue) and passes the block (pro->acc) to gp_raster_backward_impl for the same saved state.
 // pro->armed stays false where the stand-alone prologue has to run (nothing rendered, nothing saved)
 int gp_raster_backward_prepare(const gp_raster_settings* st, const gp_raster_inputs* in, const gp_raster_saved* saved, gp_alloc_fn alloc,
                                void* alloc_ctx, GpLossPrologue* pro) {
-    bwd_prepared_slot()->armed = false;
     pro->armed = false;
     RasterDims d;
     if (make_dims(st, in, d)) return 1;
@@ -325,13 +313,13 @@ int gp_raster_backward_prepare(const gp_raster_settings* st, const gp_raster_inp
     pro->ranges = il.ranges; pro->tile_work = il.tile_work; pro->T = (int)T;
     pro->order = (uint32_t*)((char*)acc + gp_align_up(acc_floats * 4, 256));
     pro->acc = acc; pro->acc_floats = acc_floats; pro->armed = true;
-    *bwd_prepared_slot() = GpBwdPrepared{saved->image, acc, acc_floats, true};
     return 0;
 }
 
-extern "C" int gp_raster_backward(const gp_raster_settings* st, const gp_raster_inputs* in, const gp_raster_outputs* fwd,
-                                  const gp_raster_saved* saved, const float* dL_dcolor, const float* dL_ddepth,
-                                  gp_raster_grads* g, gp_alloc_fn alloc, void* alloc_ctx, gp_stream_t stream_) {
+// `prepared_acc` (NULL: none): the block of gp_raster_backward_prepare for the same arguments, its prologue already enqueued
+int gp_raster_backward_impl(const gp_raster_settings* st, const gp_raster_inputs* in, const gp_raster_outputs* fwd,
+                            const gp_raster_saved* saved, const float* dL_dcolor, const float* dL_ddepth, gp_raster_grads* g,
+                            gp_alloc_fn alloc, void* alloc_ctx, gp_stream_t stream_, float* prepared_acc) {
     hipStream_t s = (hipStream_t)stream_;
     RasterDims d;
     if (make_dims(st, in, d)) return 1;
@@ -367,10 +355,8 @@ extern "C" int gp_raster_backward(const gp_raster_settings* st, const gp_raster_
 
     const size_t acc_floats = (size_t)GP_ACC_STRIDE * N;
     // (gp_train_step_run: the block was obtained ahead of the loss, and the loss launch carried the prologue -- gp_raster_backward_prepare)
-    GpBwdPrepared* pre = bwd_prepared_slot();
-    const bool prepared = pre->armed && pre->image == saved->image && pre->acc_floats == acc_floats && R > 0;
-    pre->armed = false;
-    float* acc = prepared ? pre->acc : (float*)alloc(alloc_ctx, GP_BUF_TEMP, gp_align_up(acc_floats * 4, 256) + gp_align_up(T * 4, 256));
+    const bool prepared = prepared_acc && R > 0;
+    float* acc = prepared ? prepared_acc : (float*)alloc(alloc_ctx, GP_BUF_TEMP, gp_align_up(acc_floats * 4, 256) + gp_align_up(T * 4, 256));
     if (!acc) GP_FAIL("allocator returned NULL for TEMP");
     uint32_t* order_bwd = (uint32_t*)((char*)acc + gp_align_up(acc_floats * 4, 256));
     if (prepared) {            // (both done inside the loss launch)
@@ -423,6 +409,11 @@ extern "C" int gp_raster_backward(const gp_raster_settings* st, const gp_raster_
         GP_LAUNCH_CHECK();
     }
     return 0;
+}
+extern "C" int gp_raster_backward(const gp_raster_settings* st, const gp_raster_inputs* in, const gp_raster_outputs* fwd,
+                                  const gp_raster_saved* saved, const float* dL_dcolor, const float* dL_ddepth,
+                                  gp_raster_grads* g, gp_alloc_fn alloc, void* alloc_ctx, gp_stream_t stream_) {
+    return gp_raster_backward_impl(st, in, fwd, saved, dL_dcolor, dL_ddepth, g, alloc, alloc_ctx, stream_, nullptr);
 }
 
 extern "C" int gp_debug_counters(uint64_t* out4) {

@@ -3,14 +3,7 @@
 // nothing is re-implemented here, so the fused step and the drop-in surfaces cannot drift apart.
 // [REF train.py:101-133, 196-197; scene/gaussian_model.py:251-273]
 #include "gp_common.h"
-#include "loss_adam_kernels.h"
-
-bool gp_mlp_backward_splits(const gp_mlp_params* p, int64_t rows);     // gp_capi_deform.hip (internal)
-void gp_mlp_backward_accumulate_dfeature_once();
-// gp_capi_raster.hip (internal): the rasterizer backward's TEMP block obtained ahead of the backward, its prologue described in `pro`
-int gp_raster_backward_prepare(const gp_raster_settings* st, const gp_raster_inputs* in, const gp_raster_saved* saved, gp_alloc_fn alloc,
-                               void* alloc_ctx, GpLossPrologue* pro);
-void gp_raster_backward_unprepare();
+#include "loss_adam_kernels.h"      // the rider structs and the _impl forms of the entry points that carry them
 
 // dst[i] += src[i]: the keypoint features take a gradient from the regulariser AND from the MLP's input (both "=" producers)
 __global__ __launch_bounds__(256) void gp_step_accumulate_kernel(float* __restrict__ dst, const float* __restrict__ src, int64_t n) {
@@ -18,9 +11,9 @@ __global__ __launch_bounds__(256) void gp_step_accumulate_kernel(float* __restri
     if (i < n) dst[i] += src[i];
 }
 
-// gp_adam_step_multi[_steps] over the tensors of `u`'s tables selected by `sel` -- launched on `stream`, or left in a rider slot
-// (loss_adam_kernels.h): ride = 1 for the keypoint MLP's data backward to carry, ride = 2 for the keypoint blend's backward
-static int step_adam(const gp_step_update* u, uint32_t sel, gp_stream_t stream, int ride = 0) {
+// gp_adam_step_multi[_steps] over the tensors of `u`'s tables selected by `sel` -- launched on `stream`, or, with `ride`, left in that
+// rider (loss_adam_kernels.h) for another launch to carry
+static int step_adam(const gp_step_update* u, uint32_t sel, gp_stream_t stream, GpAdamRider* ride = nullptr) {
     float *P[32], *G[32], *M[32], *V[32];
     int64_t NUM[32], ST[32];
     float LR[32];
@@ -35,15 +28,15 @@ static int step_adam(const gp_step_update* u, uint32_t sel, gp_stream_t stream, 
         ++n;
     }
     if (n == 0) return 0;
-    if (ride == 2) return gp_blend_rider_arm_adam(n, P, G, M, V, NUM, LR, ST, u->beta1, u->beta2, u->eps, 1, keep, u->skip_flag);
-    if (ride) return gp_adam_rider_arm(n, P, G, M, V, NUM, LR, ST, u->beta1, u->beta2, u->eps, 1, keep, u->skip_flag);
+    if (ride) return gp_adam_rider_fill(ride, n, P, G, M, V, NUM, LR, ST, u->beta1, u->beta2, u->eps, 1, keep, u->skip_flag);
     return gp_adam_step_multi_steps(n, P, G, M, V, NUM, LR, ST, u->beta1, u->beta2, u->eps, 1, keep, u->skip_flag, stream);
 }
 
 // Riders (gp_debug_option(15, bits): bit 0 / 1 / 2 switch A / B / C off, for A/B runs in one process; 0 = all on).  Work that sat on the
 // step's serial chain of launches although nothing in front of it produces what it needs, or nothing behind it needs what it
 // produces, travels as extra workgroups of a launch that is bound by something else -- never on a second stream, never with a
-// flag or a wait between workgroups:
+// flag or a wait between workgroups.  The passengers are structs on this call's stack (loss_adam_kernels.h), passed to the _impl form
+// of the carrying entry point, which clears the `armed` flag of what it carried; what comes back armed is launched on its own here:
 //   A  the composite backward's prologue (tile order + 64 B per Gaussian of zero fill) in the fused loss launch (vector-ALU-bound);
 //   B  the loss finalize (one workgroup; only the host reads the scalar) in the keypoint blend's backward launch;
 //   C  the Adam chunks of _scaling / _opacity (gradients final behind the projection backward) in that same launch.
@@ -53,13 +46,7 @@ extern "C" int gp_train_step_run(const gp_step_plan* p, const gp_step_view* v, c
                                  void* alloc_ctx, gp_stream_t stream) {
     bool temp_open = false;         // the backward's TEMP block was obtained ahead of the loss and its GP_BUF_TEMP_DONE is still due
     const int rc = train_step_run(p, v, u, alloc, alloc_ctx, stream, temp_open);
-    if (rc) {       // a slot left armed by a failed call must not travel with the next one
-        gp_adam_rider_slot()->armed = false;
-        gp_blend_rider_disarm();
-        gp_loss_prologue_slot()->armed = false;
-        gp_raster_backward_unprepare();
-        if (temp_open) alloc(alloc_ctx, GP_BUF_TEMP_DONE, 0);
-    }
+    if (rc && temp_open) alloc(alloc_ctx, GP_BUF_TEMP_DONE, 0);
     return rc;
 }
 static int train_step_run(const gp_step_plan* p, const gp_step_view* v, const gp_step_update* u, gp_alloc_fn alloc, void* alloc_ctx,
@@ -130,19 +117,22 @@ static int train_step_run(const gp_step_plan* p, const gp_step_view* v, const gp
     float* dimg = p->dL_dimage;
     if (!dimg) GP_FAIL("gp_train_step_run: null intermediate buffer");
     const int riders_off = gp_debug_get(15);
-    bool finalize_rides = false;
+    GpLossPrologue pro;             // rider A
+    pro.armed = false;
+    GpBlendRider blend_riders;      // riders B and C
+    blend_riders.fin_armed = blend_riders.adam.armed = false;
     if (gp_debug_get(11) == 0) {
         // one launch: the sums of the loss and its image gradient (round 6; gp_debug_option(11, 1): the pair of kernels, for A/B)
-        if (!(riders_off & 1)) {        // rider A
-            GpLossPrologue pro;
+        if (!(riders_off & 1)) {        // rider A: the backward's TEMP block ahead of the loss, its prologue in the loss launch
             if (gp_raster_backward_prepare(&st, &in, &saved, alloc, alloc_ctx, &pro)) return 1;
-            if (pro.armed) { temp_open = true; *gp_loss_prologue_slot() = pro; }
+            temp_open = pro.armed;
         }
-        if (gp_loss_l1_ssim_fused(out.color, v->gt_image, 3, H, W, p->lambda_dssim, nullptr, p->loss_sums, dimg, reg ? p->keypoint_features : nullptr,
-                                  nfeat, p->reg_scale, reg ? p->g_keypoint_features : nullptr, stream)) return 1;
-        if (!(riders_off & 2)) {        // rider B: the blend backward's launch carries the finalize (or gp_blend_rider_flush launches it)
-            if (gp_blend_rider_arm_finalize(p->loss_sums, 3, H, W, p->lambda_dssim, reg ? p->keypoint_features : nullptr, nfeat, p->reg_scale, p->loss)) return 1;
-            finalize_rides = true;
+        if (gp_loss_l1_ssim_fused_impl(out.color, v->gt_image, 3, H, W, p->lambda_dssim, nullptr, p->loss_sums, dimg, reg ? p->keypoint_features : nullptr,
+                                       nfeat, p->reg_scale, reg ? p->g_keypoint_features : nullptr, stream, &pro)) return 1;
+        if (!(riders_off & 2)) {        // rider B: the blend backward's launch carries the finalize
+            if (gp_loss_finalize_fill(&blend_riders.fin, p->loss_sums, 3, H, W, p->lambda_dssim, reg ? p->keypoint_features : nullptr, nfeat,
+                                      p->reg_scale, p->loss)) return 1;
+            blend_riders.fin_armed = true;
         } else if (reg) { if (gp_loss_l1_ssim_finalize_reg(p->loss_sums, 3, H, W, p->lambda_dssim, p->keypoint_features, nfeat, p->reg_scale, p->loss, stream)) return 1; }
         else if (gp_loss_l1_ssim_finalize(p->loss_sums, 3, H, W, p->lambda_dssim, p->loss, stream)) return 1;
     } else {
@@ -168,8 +158,7 @@ static int train_step_run(const gp_step_plan* p, const gp_step_view* v, const gp
     memset(&g, 0, sizeof(g));
     g.dL_dmeans3D = p->g_xyz_t; g.dL_dmeans2D = p->g_means2D; g.dL_dshs = p->g_features_dc; g.dL_dshs_rest = p->g_features_rest;
     g.dL_dopacities = raw_act ? p->g_opacity : p->g_opacity_t; g.dL_dscales = raw_act ? p->g_scaling : p->g_scale; g.dL_drotations = p->g_q_t; g.accumulate_shs = 0; g.adam_shs = u->adam_shs;
-    if (gp_raster_backward(&st, &in, &out, &saved, dimg, nullptr, &g, alloc, alloc_ctx, stream)) return 1;
-    gp_raster_backward_unprepare();
+    if (gp_raster_backward_impl(&st, &in, &out, &saved, dimg, nullptr, &g, alloc, alloc_ctx, stream, pro.armed ? pro.acc : nullptr)) return 1;
     alloc(alloc_ctx, GP_BUF_TEMP_DONE, 0);
     temp_open = false;
     if (u->hook) u->hook(u->hook_ctx, GP_STEP_AFTER_RASTER_BACKWARD);
@@ -182,25 +171,27 @@ static int train_step_run(const gp_step_plan* p, const gp_step_view* v, const gp
     if (!(riders_off & 4) && raw_act && !u->hook)
         for (int k = 0; k < u->adam_count; ++k)
             if (u->adam_params[k] == p->scaling || u->adam_params[k] == p->opacity) rode |= 1u << k;
-    if (rode && step_adam(u, rode, stream, 2)) return 1;
-    if (gp_blend_backward(&ba, p->g_xyz_t, p->g_q_t, p->g_delta, nullptr, p->g_xyz, p->g_rotation, alloc, alloc_ctx, stream)) return 1;
+    if (rode && step_adam(u, rode, stream, &blend_riders.adam)) return 1;
+    if (gp_blend_backward_impl(&ba, p->g_xyz_t, p->g_q_t, p->g_delta, nullptr, p->g_xyz, p->g_rotation, alloc, alloc_ctx, stream, &blend_riders)) return 1;
     alloc(alloc_ctx, GP_BUF_TEMP_DONE, 0);
-    if ((finalize_rides || rode) && gp_blend_rider_flush((hipStream_t)stream)) return 1;     // (what the launch could not carry: on its own)
+    // (what the launch could not carry: on its own)
+    if (blend_riders.fin_armed && gp_loss_finalize_launch(blend_riders.fin, (hipStream_t)stream)) return 1;
+    if (gp_adam_rider_launch(&blend_riders.adam, (hipStream_t)stream)) return 1;
     // ---- optimizer, first part [REF train.py:196-197]: the per-Gaussian tensors' gradients are final here.  Their update (HBM-bound,
     // every CU) needs nothing the keypoint MLP's backward (latency-bound, 16 CUs) produces and touches none of its tensors: the tensors of
     // adam_early_mask RIDE in the launch of that backward's data kernel (the rider of loss_adam_kernels.h; a row count the small-row
     // kernels do not serve leaves the rider unconsumed: it is then launched right behind the MLP backward).
     const uint32_t early = (u->hook || u->adam_count <= 0) ? 0u : (u->adam_early_mask & all & ~rode);
-    if (early && step_adam(u, early, stream, true)) return 1;
+    GpAdamRider mlp_rider;
+    mlp_rider.armed = false;
+    if (early && step_adam(u, early, stream, &mlp_rider)) return 1;
     gp_mlp_grads mg = p->g_mlp;
     // (the keypoint features take a gradient from the regulariser -- written by the loss kernel -- AND from the MLP's input: the
     // feature-split data backward adds its part in place; the 16-row form writes a temporary that a launch of its own adds)
     const bool add_in_place = reg && gp_mlp_backward_splits(&p->mlp, K);
-    if (add_in_place) gp_mlp_backward_accumulate_dfeature_once();
-    const int rc_mlp = gp_mlp_backward(&p->mlp, &mi, p->acts, p->g_delta, &mg, (reg && !add_in_place) ? p->g_feature_tmp : p->g_keypoint_features,
-                                       p->g_keypoints, alloc, alloc_ctx, stream);
-    if (rc_mlp) return 1;       // (gp_train_step_run disarms the rider slots on every error return)
-    if (gp_adam_rider_flush((hipStream_t)stream)) return 1;
+    if (gp_mlp_backward_impl(&p->mlp, &mi, p->acts, p->g_delta, &mg, (reg && !add_in_place) ? p->g_feature_tmp : p->g_keypoint_features,
+                             p->g_keypoints, alloc, alloc_ctx, stream, &mlp_rider, add_in_place)) return 1;
+    if (gp_adam_rider_launch(&mlp_rider, (hipStream_t)stream)) return 1;
     if (reg && !add_in_place) {
         hipLaunchKernelGGL(gp_step_accumulate_kernel, dim3(gp_blocks((size_t)nfeat, 256)), dim3(256), 0, (hipStream_t)stream,
                            p->g_keypoint_features, (const float*)p->g_feature_tmp, nfeat);

@@ -1,7 +1,8 @@
 // loss_adam_kernels.h -- the multi-tensor Adam launch's table and chunk body (shared by gp_adam_multi_kernel and by the launches that
 // carry the same chunks: the keypoint MLP's data backward, deform_mlp_small.hip, and the keypoint blend's backward, deform_kernels.hip),
-// the loss finalize's body (the blend backward's launch carries it too), and the "rider" slots through which gp_train_step_run hands
-// those launches their passengers.  Everything else of loss_adam_kernels.hip is private to it.
+// the loss finalize's body (the blend backward's launch carries it too), and the fused step's internal interface: the "rider" structs
+// that gp_train_step_run keeps on its stack and the _impl forms of the carrying entry points that take them as arguments (the public
+// entry points of include/gp_hip.h are wrappers that pass "no riders").  Everything else of loss_adam_kernels.hip is private to it.
 #pragma once
 #include "gp_common.h"
 
@@ -75,8 +76,8 @@ __device__ __forceinline__ void adam_chunk_body(const AdamTable& t, unsigned chu
 
 // The rider: an optimizer launch whose tensors need nothing the keypoint MLP's backward produces (the per-Gaussian tensors: HBM-bound,
 // every CU) travels in the SAME launch as that backward's data kernel (16 workgroups, bound by the rate at which one CU takes the
-// weights in) -- gp_train_step_run arms the slot, gp_mlp_backward's small-row path consumes it; an unconsumed rider is launched on
-// its own (gp_adam_rider_flush).  One slot per host thread: arm, consume and flush happen inside ONE call of gp_train_step_run.
+// weights in) -- gp_train_step_run fills the struct and passes it to gp_mlp_backward_impl, whose small-row path carries it and clears
+// `armed`; a rider that comes back armed is launched on its own (gp_adam_rider_launch).  Host-only.
 struct GpAdamRider {
     AdamTable t;
     float b1, b2, eps;
@@ -85,12 +86,15 @@ struct GpAdamRider {
     unsigned chunks;
     bool armed;
 };
-GpAdamRider* gp_adam_rider_slot();
-// fills the slot from the optimizer's arrays (the arguments of gp_adam_step_multi_steps); armed unless there is nothing to update
-int gp_adam_rider_arm(int count, float* const* params, float* const* grads, float* const* exp_avgs, float* const* exp_avg_sqs,
-                      const int64_t* numels, const float* lrs, const int64_t* steps, float beta1, float beta2, float eps, int zero_grad,
-                      uint32_t keep_grad_mask, const uint32_t* skip_flag);
-int gp_adam_rider_flush(hipStream_t s);     // launches an armed rider as a plain gp_adam_multi_kernel and disarms the slot
+// fills `r` from the optimizer's arrays (the arguments of gp_adam_step_multi_steps); armed unless there is nothing to update
+int gp_adam_rider_fill(GpAdamRider* r, int count, float* const* params, float* const* grads, float* const* exp_avgs,
+                       float* const* exp_avg_sqs, const int64_t* numels, const float* lrs, const int64_t* steps, float beta1, float beta2,
+                       float eps, int zero_grad, uint32_t keep_grad_mask, const uint32_t* skip_flag);
+int gp_adam_rider_launch(GpAdamRider* r, hipStream_t s);    // an armed rider as a plain gp_adam_multi_kernel (scope "adam"); disarms it
+int gp_mlp_backward_impl(const gp_mlp_params* p, const gp_mlp_input* x, const float* acts, const float* dL_dout, gp_mlp_grads* g,
+                         float* dL_dfeature, float* dL_dxyz, gp_alloc_fn alloc, void* alloc_ctx, gp_stream_t stream, GpAdamRider* rider,
+                         bool accumulate_dfeature);         // (rider may be NULL; "+=" into dL_dfeature: the feature-split kernel only)
+bool gp_mlp_backward_splits(const gp_mlp_params* p, int64_t rows);      // would it take the feature-split data kernel?
 
 // ---- the loss scalar: loss = (1-lam) * sums[0]/n + lam * (1 - sums[1]/n) [+ scale/n * sum|x|], one 256-thread workgroup
 __device__ __forceinline__ float block_sum_256(float v, float* s_red) {
@@ -167,13 +171,17 @@ __device__ __forceinline__ void loss_finalize_body(const LossFinalizeDev& f, flo
     }
 }
 
-// ---- riders of the keypoint blend's backward launch (gp_blend_backward, nn = 6 / 8 kernels; deform_kernels.hip).  That launch is bound
-// by its own instruction stream and leaves HBM half idle; gp_train_step_run puts into it, as workgroups IN FRONT of the blend's own:
+// (validated; x may be NULL: no regulariser term)
+int gp_loss_finalize_fill(LossFinalizeDev* f, const double* sums, int32_t channels, int32_t H, int32_t W, float lambda_dssim, const float* x,
+                          int64_t n, float scale, float* loss);
+int gp_loss_finalize_launch(const LossFinalizeDev& f, hipStream_t s);   // one workgroup of its own (gp_loss_finalize_reg_kernel)
+
+// ---- riders of the keypoint blend's backward launch (gp_blend_backward_impl, nn = 6 / 8 kernels; deform_kernels.hip).  That launch is
+// bound by its own instruction stream and leaves HBM half idle; gp_train_step_run puts into it, as workgroups IN FRONT of the blend's own:
 //   * the loss finalize (one workgroup): nothing on the device reads the scalar, and the launch runs before every optimizer launch
 //     that moves the regulariser's input;
 //   * the Adam chunks of the tensors whose gradients the projection backward has already finished (_scaling, _opacity).
-// Armed by gp_train_step_run only, consumed by gp_blend_backward (which clears the flags of what it carried); whatever is still armed
-// afterwards is launched on its own (gp_blend_rider_flush).  One slot per host thread.
+// gp_blend_backward_impl clears the flags of what it carried; whatever comes back armed its caller launches on its own.
 struct BlendRideDev {
     AdamTable t;
     float b1, b2, eps;
@@ -183,23 +191,18 @@ struct BlendRideDev {
     unsigned fin_blocks;        // 0 / 1: workgroup 0 is the loss finalize
     LossFinalizeDev fin;
 };
-struct GpBlendRider {
+struct GpBlendRider {           // host-only
     GpAdamRider adam;
     LossFinalizeDev fin;
     bool fin_armed;
 };
-GpBlendRider* gp_blend_rider_slot();
-int gp_blend_rider_arm_adam(int count, float* const* params, float* const* grads, float* const* exp_avgs, float* const* exp_avg_sqs,
-                            const int64_t* numels, const float* lrs, const int64_t* steps, float beta1, float beta2, float eps,
-                            int zero_grad, uint32_t keep_grad_mask, const uint32_t* skip_flag);
-int gp_blend_rider_arm_finalize(const double* sums, int32_t channels, int32_t H, int32_t W, float lambda_dssim, const float* x, int64_t n,
-                                float scale, float* loss);
-int gp_blend_rider_flush(hipStream_t s);    // launches what is still armed on its own and disarms the slot
-void gp_blend_rider_disarm();
+int gp_blend_backward_impl(const gp_blend_args* a, const float* dL_dxyz_t, const float* dL_dq_t, float* dL_ddelta, float* dL_draw_w,
+                           float* dL_dxyz, float* dL_drot, gp_alloc_fn alloc, void* alloc_ctx, gp_stream_t stream, GpBlendRider* riders);
 
-// ---- rider of the fused loss launch (gp_loss_l1_ssim_fused): the composite backward's prologue -- its tile order (needs the composite
-// FORWARD's ranges and tile_work only) and the zero fill of its accumulators (needs nothing).  gp_train_step_run obtains the block
-// from gp_raster_backward_prepare (gp_capi_raster.hip) and arms the slot; the next gp_loss_l1_ssim_fused call consumes it.
+// ---- rider of the fused loss launch (gp_loss_l1_ssim_fused_impl): the composite backward's prologue -- its tile order (needs the
+// composite FORWARD's ranges and tile_work only) and the zero fill of its accumulators (needs nothing).  gp_train_step_run obtains the
+// backward's TEMP block ahead of the loss (gp_raster_backward_prepare, gp_capi_raster.hip: `pro` describes the prologue, armed = false
+// where the stand-alone prologue has to run), hands `pro` to the loss launch and pro.acc to gp_raster_backward_impl as `prepared_acc`.
 struct GpLossPrologue {
     const int2* ranges;
     const int32_t* tile_work;
@@ -209,4 +212,11 @@ struct GpLossPrologue {
     size_t acc_floats;
     bool armed;
 };
-GpLossPrologue* gp_loss_prologue_slot();
+int gp_raster_backward_prepare(const gp_raster_settings* st, const gp_raster_inputs* in, const gp_raster_saved* saved, gp_alloc_fn alloc,
+                               void* alloc_ctx, GpLossPrologue* pro);
+int gp_loss_l1_ssim_fused_impl(const float* img, const float* gt, int32_t channels, int32_t H, int32_t W, float lambda_dssim,
+                               const float* upstream, double* sums, float* dimg, const float* x, int64_t n, float scale, float* gx,
+                               gp_stream_t stream, const GpLossPrologue* pro);       // (pro may be NULL)
+int gp_raster_backward_impl(const gp_raster_settings* st, const gp_raster_inputs* in, const gp_raster_outputs* fwd,
+                            const gp_raster_saved* saved, const float* dL_dcolor, const float* dL_ddepth, gp_raster_grads* g,
+                            gp_alloc_fn alloc, void* alloc_ctx, gp_stream_t stream, float* prepared_acc);    // (NULL: obtains its own)

@@ -534,11 +534,27 @@ extern "C" int gp_loss_l1_ssim_forward(const float* img, const float* gt, int32_
     return 0;
 }
 
-extern "C" int gp_loss_l1_ssim_finalize(const double* sums, int32_t channels, int32_t H, int32_t W, float lambda_dssim, float* loss,
-                                        gp_stream_t stream_) {
+// the finalize's arguments, validated (loss_adam_kernels.h; x may be NULL: no regulariser term)
+int gp_loss_finalize_fill(LossFinalizeDev* f, const double* sums, int32_t channels, int32_t H, int32_t W, float lambda_dssim, const float* x,
+                          int64_t n, float scale, float* loss) {
     if (!sums || !loss) GP_FAIL("null argument");
     if (((uintptr_t)sums & 15) != 0) GP_FAIL("sums must be 16-byte aligned");
-    hipLaunchKernelGGL(gp_loss_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream_, sums, (int)GP_LOSS_SUM_SLOTS(H, W), (double)channels * H * W, lambda_dssim, loss);
+    if (x && (n <= 0 || n > GP_LOSS_REG_MAX)) GP_FAIL("regulariser input must have 1..%d elements (use gp_l1_mean_forward beyond)", GP_LOSS_REG_MAX);
+    *f = LossFinalizeDev{sums, (int)GP_LOSS_SUM_SLOTS(H, W), (double)channels * H * W, lambda_dssim, x, x ? (long)n : 0L,
+                         x ? scale / (float)n : 0.f, loss};
+    return 0;
+}
+int gp_loss_finalize_launch(const LossFinalizeDev& f, hipStream_t s) {
+    hipLaunchKernelGGL(gp_loss_finalize_reg_kernel, dim3(1), dim3(256), 0, s, f);
+    GP_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int gp_loss_l1_ssim_finalize(const double* sums, int32_t channels, int32_t H, int32_t W, float lambda_dssim, float* loss,
+                                        gp_stream_t stream_) {
+    LossFinalizeDev f;
+    if (gp_loss_finalize_fill(&f, sums, channels, H, W, lambda_dssim, nullptr, 0, 0.f, loss)) return 1;
+    hipLaunchKernelGGL(gp_loss_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream_, f.sums, f.nslots, f.n, f.lambda, f.loss);
     GP_LAUNCH_CHECK();
     return 0;
 }
@@ -555,15 +571,15 @@ extern "C" int gp_loss_l1_ssim_backward(const float* img, const float* gt, const
     return 0;
 }
 
-// forward sums + image gradient in one launch (gp_l1_ssim_fused_kernel); the loss value still comes from a finalize call on `sums`
-extern "C" int gp_loss_l1_ssim_fused(const float* img, const float* gt, int32_t channels, int32_t H, int32_t W, float lambda_dssim,
-                                     const float* upstream, double* sums, float* dimg, const float* x, int64_t n, float scale, float* gx,
-                                     gp_stream_t stream_) {
+// forward sums + image gradient in one launch (gp_l1_ssim_fused_kernel); the loss value still comes from a finalize call on `sums`.
+// `pro_in` (gp_train_step_run; NULL or not armed: none): the composite backward's prologue travels in the launch.
+int gp_loss_l1_ssim_fused_impl(const float* img, const float* gt, int32_t channels, int32_t H, int32_t W, float lambda_dssim,
+                               const float* upstream, double* sums, float* dimg, const float* x, int64_t n, float scale, float* gx,
+                               gp_stream_t stream_, const GpLossPrologue* pro_in) {
     hipStream_t s = (hipStream_t)stream_;
-    // the composite backward's prologue, if gp_train_step_run left one for this launch (consumed or dropped here, whatever happens)
-    GpLossPrologue pro = *gp_loss_prologue_slot();
-    gp_loss_prologue_slot()->armed = false;
-    if (!pro.armed) memset(&pro, 0, sizeof(pro));
+    GpLossPrologue pro;
+    if (pro_in && pro_in->armed) pro = *pro_in;
+    else memset(&pro, 0, sizeof(pro));
     if (!img || !gt || !sums || !dimg) GP_FAIL("null argument");
     if (channels != 3 || H <= 0 || W <= 0) GP_FAIL("expects a [3,H,W] image (got C=%d H=%d W=%d)", channels, H, W);
     if ((x != nullptr) != (gx != nullptr)) GP_FAIL("regulariser input and gradient must be given together");
@@ -575,18 +591,20 @@ extern "C" int gp_loss_l1_ssim_fused(const float* img, const float* gt, int32_t 
     GP_LAUNCH_CHECK();
     return 0;
 }
+extern "C" int gp_loss_l1_ssim_fused(const float* img, const float* gt, int32_t channels, int32_t H, int32_t W, float lambda_dssim,
+                                     const float* upstream, double* sums, float* dimg, const float* x, int64_t n, float scale, float* gx,
+                                     gp_stream_t stream_) {
+    return gp_loss_l1_ssim_fused_impl(img, gt, channels, H, W, lambda_dssim, upstream, sums, dimg, x, n, scale, gx, stream_, nullptr);
+}
 
 // the two calls above with the regulariser  scale * mean|x|  [REF scene/gaussian_model.py:174-178] folded in (x small: the
 // keypoint features of stage 2/3) -- saves the regulariser's own forward and backward launches
 extern "C" int gp_loss_l1_ssim_finalize_reg(const double* sums, int32_t channels, int32_t H, int32_t W, float lambda_dssim,
                                             const float* x, int64_t n, float scale, float* loss, gp_stream_t stream_) {
-    if (!sums || !loss || !x) GP_FAIL("null argument");
-    if (((uintptr_t)sums & 15) != 0) GP_FAIL("sums must be 16-byte aligned");
-    if (n <= 0 || n > GP_LOSS_REG_MAX) GP_FAIL("regulariser input must have 1..%d elements (use gp_l1_mean_forward beyond)", GP_LOSS_REG_MAX);
-    LossFinalizeDev f = {sums, (int)GP_LOSS_SUM_SLOTS(H, W), (double)channels * H * W, lambda_dssim, x, (long)n, scale / (float)n, loss};
-    hipLaunchKernelGGL(gp_loss_finalize_reg_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream_, f);
-    GP_LAUNCH_CHECK();
-    return 0;
+    if (!x) GP_FAIL("null argument");
+    LossFinalizeDev f;
+    if (gp_loss_finalize_fill(&f, sums, channels, H, W, lambda_dssim, x, n, scale, loss)) return 1;
+    return gp_loss_finalize_launch(f, (hipStream_t)stream_);
 }
 extern "C" int gp_loss_l1_ssim_backward_reg(const float* img, const float* gt, const float* dmaps, int32_t channels, int32_t H, int32_t W,
                                             float lambda_dssim, const float* upstream, float* dimg, const float* x, int64_t n,
@@ -651,30 +669,10 @@ static int adam_build_table(AdamTable& t, long& n_chunks, int32_t count, float* 
     return 0;
 }
 
-extern "C" int gp_adam_step_multi_steps(int32_t count, float* const* params, float* const* grads, float* const* exp_avgs,
-                                        float* const* exp_avg_sqs, const int64_t* numels, const float* lrs, const int64_t* steps,
-                                        float beta1, float beta2, float eps, int32_t zero_grad, uint32_t keep_grad_mask,
-                                        const uint32_t* skip_flag, gp_stream_t stream_) {
-    hipStream_t s = (hipStream_t)stream_;
-    AdamTable t;
-    long chunks = 0;
-    if (adam_build_table(t, chunks, count, params, grads, exp_avgs, exp_avg_sqs, numels, lrs, steps, beta1, beta2, keep_grad_mask)) return 1;
-    if (chunks == 0) return 0;
-    GpProfScope _p("adam", s);
-    hipLaunchKernelGGL(gp_adam_multi_kernel, dim3((unsigned)chunks), dim3(256), 0, s, t, beta1, beta2, eps, zero_grad, skip_flag);
-    GP_LAUNCH_CHECK();
-    return 0;
-}
-
-// ---- the rider (loss_adam_kernels.h)
-GpAdamRider* gp_adam_rider_slot() {
-    static thread_local GpAdamRider slot = {};
-    return &slot;
-}
-int gp_adam_rider_arm(int count, float* const* params, float* const* grads, float* const* exp_avgs, float* const* exp_avg_sqs,
-                      const int64_t* numels, const float* lrs, const int64_t* steps, float beta1, float beta2, float eps, int zero_grad,
-                      uint32_t keep_grad_mask, const uint32_t* skip_flag) {
-    GpAdamRider* r = gp_adam_rider_slot();
+// ---- the rider form of one multi-tensor launch (loss_adam_kernels.h): filled here, launched here or carried by another launch
+int gp_adam_rider_fill(GpAdamRider* r, int count, float* const* params, float* const* grads, float* const* exp_avgs,
+                       float* const* exp_avg_sqs, const int64_t* numels, const float* lrs, const int64_t* steps, float beta1, float beta2,
+                       float eps, int zero_grad, uint32_t keep_grad_mask, const uint32_t* skip_flag) {
     r->armed = false;
     long chunks = 0;
     if (adam_build_table(r->t, chunks, count, params, grads, exp_avgs, exp_avg_sqs, numels, lrs, steps, beta1, beta2, keep_grad_mask)) return 1;
@@ -682,8 +680,7 @@ int gp_adam_rider_arm(int count, float* const* params, float* const* grads, floa
     r->armed = chunks > 0;
     return 0;
 }
-int gp_adam_rider_flush(hipStream_t s) {
-    GpAdamRider* r = gp_adam_rider_slot();
+int gp_adam_rider_launch(GpAdamRider* r, hipStream_t s) {
     if (!r->armed) return 0;
     r->armed = false;
     GpProfScope _p("adam", s);
@@ -692,58 +689,14 @@ int gp_adam_rider_flush(hipStream_t s) {
     return 0;
 }
 
-// ---- the riders of the blend backward's launch and of the fused loss launch (loss_adam_kernels.h)
-GpBlendRider* gp_blend_rider_slot() {
-    static thread_local GpBlendRider slot = {};
-    return &slot;
-}
-void gp_blend_rider_disarm() {
-    GpBlendRider* r = gp_blend_rider_slot();
-    r->adam.armed = false;
-    r->fin_armed = false;
-}
-int gp_blend_rider_arm_adam(int count, float* const* params, float* const* grads, float* const* exp_avgs, float* const* exp_avg_sqs,
-                            const int64_t* numels, const float* lrs, const int64_t* steps, float beta1, float beta2, float eps,
-                            int zero_grad, uint32_t keep_grad_mask, const uint32_t* skip_flag) {
-    GpAdamRider* r = &gp_blend_rider_slot()->adam;
-    r->armed = false;
-    long chunks = 0;
-    if (adam_build_table(r->t, chunks, count, params, grads, exp_avgs, exp_avg_sqs, numels, lrs, steps, beta1, beta2, keep_grad_mask)) return 1;
-    r->b1 = beta1; r->b2 = beta2; r->eps = eps; r->zero_grad = zero_grad; r->skip_flag = skip_flag; r->chunks = (unsigned)chunks;
-    r->armed = chunks > 0;
-    return 0;
-}
-int gp_blend_rider_arm_finalize(const double* sums, int32_t channels, int32_t H, int32_t W, float lambda_dssim, const float* x, int64_t n,
-                                float scale, float* loss) {
-    GpBlendRider* r = gp_blend_rider_slot();
-    r->fin_armed = false;
-    if (!sums || !loss) GP_FAIL("null argument");
-    if (((uintptr_t)sums & 15) != 0) GP_FAIL("sums must be 16-byte aligned");
-    if (x && (n <= 0 || n > GP_LOSS_REG_MAX)) GP_FAIL("regulariser input must have 1..%d elements", GP_LOSS_REG_MAX);
-    r->fin = LossFinalizeDev{sums, (int)GP_LOSS_SUM_SLOTS(H, W), (double)channels * H * W, lambda_dssim, x, x ? (long)n : 0L,
-                             x ? scale / (float)n : 0.f, loss};
-    r->fin_armed = true;
-    return 0;
-}
-int gp_blend_rider_flush(hipStream_t s) {
-    GpBlendRider* r = gp_blend_rider_slot();
-    const bool fin = r->fin_armed, adam = r->adam.armed;
-    gp_blend_rider_disarm();
-    if (fin) {
-        hipLaunchKernelGGL(gp_loss_finalize_reg_kernel, dim3(1), dim3(256), 0, s, r->fin);
-        GP_LAUNCH_CHECK();
-    }
-    if (adam) {
-        GpProfScope _p("adam", s);
-        hipLaunchKernelGGL(gp_adam_multi_kernel, dim3(r->adam.chunks), dim3(256), 0, s, r->adam.t, r->adam.b1, r->adam.b2, r->adam.eps,
-                           r->adam.zero_grad, r->adam.skip_flag);
-        GP_LAUNCH_CHECK();
-    }
-    return 0;
-}
-GpLossPrologue* gp_loss_prologue_slot() {
-    static thread_local GpLossPrologue slot = {};
-    return &slot;
+extern "C" int gp_adam_step_multi_steps(int32_t count, float* const* params, float* const* grads, float* const* exp_avgs,
+                                        float* const* exp_avg_sqs, const int64_t* numels, const float* lrs, const int64_t* steps,
+                                        float beta1, float beta2, float eps, int32_t zero_grad, uint32_t keep_grad_mask,
+                                        const uint32_t* skip_flag, gp_stream_t stream_) {
+    GpAdamRider r;
+    if (gp_adam_rider_fill(&r, count, params, grads, exp_avgs, exp_avg_sqs, numels, lrs, steps, beta1, beta2, eps, zero_grad, keep_grad_mask,
+                           skip_flag)) return 1;
+    return gp_adam_rider_launch(&r, (hipStream_t)stream_);
 }
 
 extern "C" int gp_adam_step_multi(int32_t count, float* const* params, float* const* grads, float* const* exp_avgs,
