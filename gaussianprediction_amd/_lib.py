@@ -141,12 +141,13 @@ EXPORTS = [
     "gp_hashgrid_table_entries", "gp_hashgrid_forward", "gp_hashgrid_backward", "gp_knn_keypoints",
     "gp_weights_forward", "gp_weights_backward", "gp_l1_mean_forward", "gp_l1_mean_backward", "gp_loss_l1_ssim_finalize_reg", "gp_loss_l1_ssim_backward_reg", "gp_furthest_point_sampling", "gp_knn3_mean_dist2",
     "gp_knn_points", "gp_knn_points_backward", "gp_furthest_point_sampling_batched",
+    "gp_image_metrics", "gp_image_metrics_scratch_bytes",
     "gp_microbench_copy", "gp_microbench_read", "gp_microbench_mfma", "gp_microbench_valu", "gp_microbench_gather",
     "gp_debug_option", "gp_debug_counters", "gp_train_step_run", "gp_sh_factor_gradient",
     "gp_mlp_input_forward", "gp_mlp_input_backward", "gp_linear_forward", "gp_linear_backward", "gp_softmax_forward", "gp_softmax_backward",
     "gp_last_error", "gp_version", "gp_abi_version",
 ]
-GP_ABI_VERSION = 8         # include/gp_hip.h: the struct layouts / signatures / buffer-size macros this binding was written against
+GP_ABI_VERSION = 9         # include/gp_hip.h: the struct layouts / signatures / buffer-size macros this binding was written against
 
 _lib = None
 _lock = threading.Lock()
@@ -182,6 +183,7 @@ def lib() -> C.CDLL:
         l.gp_mlp_packed_floats.restype = C.c_int64
         l.gp_mlp_scratch_bytes.restype = C.c_int64
         l.gp_mlp16_packed_elems.restype = C.c_int64
+        l.gp_image_metrics_scratch_bytes.restype = C.c_int64
         if int(l.gp_abi_version()) != GP_ABI_VERSION:
             raise GpHipError(f"{LIB_PATH} implements ABI {int(l.gp_abi_version())}, this binding is written against ABI "
                              f"{GP_ABI_VERSION} (include/gp_hip.h): rebuild the library (__graft_entry__.build(force=True))")

@@ -1,0 +1,241 @@
+"""Image metrics on the device: L1, MSE, PSNR (both call shapes of the reference), SSIM, MS-SSIM and D-SSIM of rendered views
+against their ground truth in ONE call of libgp_hip.so (gp_image_metrics, csrc/metric_kernels.hip), and evaluation loops over it
+that never read a number back per view.
+
+  [REF metrics.py:138-147]  ssim, psnr on [1,3,H,W], ms_ssim(data_range=1), D-SSIM = (1 - MS-SSIM) / 2, the error image
+  [REF train.py:107,252-282] psnr on [3,H,W] followed by .mean(); the clamped L1 / PSNR means of training_report
+  [REF utils/loss_utils.py:54-98, utils/image_utils.py:18-20]
+
+MS-SSIM follows the published five-scale form as pytorch_msssim computes it; that package is absent here, so parity with it is
+unpinned (the definition is restated in include/gp_hip.h and checked against a float64 torch restatement in the tests).
+LPIPS is not provided: it needs pretrained network weights this package does not ship.  HIP only: CPU tensors raise."""
+from __future__ import annotations
+
+import ctypes as C
+import json
+import os
+from types import SimpleNamespace
+
+import torch
+
+from . import _lib
+
+NAMES = ("L1", "MSE", "PSNR", "PSNR_CH", "SSIM", "MS_SSIM", "D_SSIM", "reserved")
+L1, MSE, PSNR, PSNR_CH, SSIM, MS_SSIM, D_SSIM = range(7)
+METRIC_COUNT = 8
+QUANTIZE8, CLAMP01, WITH_MS_SSIM = 1, 2, 4      # GP_METRICS_* of include/gp_hip.h
+
+_scratch: dict = {}
+
+
+def metrics_scratch(device, B, H, W, flags):
+    """One scratch buffer per (device, stream, shape, flags): the calls on a stream are ordered, so the buffer is reused."""
+    key = (device.index, _lib.stream_ptr(device).value, B, H, W, flags)
+    t = _scratch.get(key)
+    if t is None:
+        n = int(_lib.lib().gp_image_metrics_scratch_bytes(C.c_int32(B), C.c_int32(H), C.c_int32(W), C.c_uint32(flags)))
+        if n < 0:
+            raise _lib.GpHipError(f"gp_image_metrics_scratch_bytes: {_lib.lib().gp_last_error().decode(errors='replace')}")
+        t = torch.empty(n + 256, dtype=torch.uint8, device=device)
+        if len(_scratch) >= 16:
+            _scratch.pop(next(iter(_scratch)))
+        _scratch[key] = t
+    return t
+
+
+def _as_batch(x, name):
+    if not torch.is_tensor(x) or not x.is_cuda:
+        raise RuntimeError(f"image_metrics: {name} must be a GPU tensor -- HIP kernels only (no CPU fallback)")
+    x = x.detach()
+    if x.dim() == 3:
+        x = x[None]
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise RuntimeError(f"image_metrics: {name} must be [B,3,H,W] or [3,H,W] (got {tuple(x.shape)})")
+    return x.to(torch.float32).contiguous()
+
+
+def image_metrics(render, gt, *, quantize8=False, clamp=False, ms_ssim=True, out=None, invalid_flag=None, levels=False,
+                  quantized=False, deltas=False):
+    """Metrics of render against gt ([B,3,H,W] or [3,H,W], any float dtype: converted to contiguous float32).  Returns a namespace:
+      table      [B,8] float64 on the device, columns `names` (L1, MSE, PSNR, PSNR_CH, SSIM, MS_SSIM, D_SSIM, reserved); nothing is
+                 read back.  `out=` (a [B,8] float64 contiguous view, e.g. rows of a caller's table) receives it instead.
+      levels     [B,5,3] float64 (levels=True): mean cs of scales 1-4 and mean ssim of scale 5 per channel, before the ReLU
+      quantized  [B,3,H,W] uint8 (quantized=True, needs quantize8): the 8-bit render
+      deltas     [B,H,W,3] uint8 (deltas=True): trunc(|render - gt| * 255), the error image of metrics.py:146-147
+    quantize8: the render goes through an 8-bit image file first (floor(x * 255 + 0.5) clamped, / 255), as every render does before
+    the reference's metrics.py sees it.  clamp: both images clamped to [0, 1] (training_report).  ms_ssim=False skips the four
+    further pyramid levels (columns 5, 6 are NaN); with it min(H, W) must exceed 160, as pytorch_msssim asserts.
+    invalid_flag: optional device word per image (int32 / uint32 [B]); non-zero turns that row into NaN."""
+    a, b = _as_batch(render, "render"), _as_batch(gt, "gt")
+    if a.shape != b.shape or a.device != b.device:
+        raise RuntimeError(f"image_metrics: render {tuple(a.shape)} on {a.device} and gt {tuple(b.shape)} on {b.device} differ")
+    dev = a.device
+    B, _, H, W = a.shape
+    flags = (QUANTIZE8 if quantize8 else 0) | (CLAMP01 if clamp else 0) | (WITH_MS_SSIM if ms_ssim else 0)
+    if levels and not ms_ssim:
+        raise RuntimeError("image_metrics: levels=True needs ms_ssim=True")
+    if quantized and not quantize8:
+        raise RuntimeError("image_metrics: quantized=True needs quantize8=True")
+    if out is None:
+        table = torch.empty(B, METRIC_COUNT, dtype=torch.float64, device=dev)
+    else:
+        table = out
+        if table.dtype != torch.float64 or table.device != dev or tuple(table.shape) != (B, METRIC_COUNT) or not table.is_contiguous():
+            raise RuntimeError(f"image_metrics: out must be a contiguous [{B},{METRIC_COUNT}] float64 tensor on {dev}")
+    if invalid_flag is not None:
+        if invalid_flag.device != dev or invalid_flag.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or invalid_flag.numel() != B \
+                or not invalid_flag.is_contiguous():
+            raise RuntimeError(f"image_metrics: invalid_flag must be {B} contiguous 32-bit words on {dev}")
+    lv = torch.empty(B, 5, 3, dtype=torch.float64, device=dev) if levels else None
+    qo = torch.empty(B, 3, H, W, dtype=torch.uint8, device=dev) if quantized else None
+    do = torch.empty(B, H, W, 3, dtype=torch.uint8, device=dev) if deltas else None
+    with _lib.on_device(dev):
+        scratch = metrics_scratch(dev, B, H, W, flags)
+        sp = (scratch.data_ptr() + 255) & ~255
+        rc = _lib.lib().gp_image_metrics(_lib.ptr(a), _lib.ptr(b), C.c_int32(B), C.c_int32(3), C.c_int32(H), C.c_int32(W), C.c_uint32(flags),
+                                         C.c_void_p(sp), _lib.ptr(invalid_flag), _lib.ptr(table), _lib.ptr(lv), _lib.ptr(qo), _lib.ptr(do),
+                                         _lib.stream_ptr(dev))
+        _lib.check(rc, "gp_image_metrics")
+    return SimpleNamespace(table=table, names=NAMES, levels=lv, quantized=qo, deltas=do)
+
+
+def psnr(img, gt):
+    """[B] (or a scalar tensor for [3,H,W]) float64: PSNR over all three channels, `psnr()` of the reference on [1,3,H,W]."""
+    t = image_metrics(img, gt, ms_ssim=False).table[:, PSNR]
+    return t[0] if img.dim() == 3 else t
+
+
+def ms_ssim(img, gt):
+    """[B] (or a scalar tensor for [3,H,W]) float64: MS-SSIM with data_range 1 (parity with pytorch_msssim is unpinned)."""
+    t = image_metrics(img, gt, ms_ssim=True).table[:, MS_SSIM]
+    return t[0] if img.dim() == 3 else t
+
+
+def _times(cameras, times, dev):
+    if times is not None:
+        return list(times)
+    return [torch.as_tensor(getattr(c, "time", 0.0), dtype=torch.float32, device=dev).reshape(1) for c in cameras]
+
+
+def evaluate_views(model, cameras, gts, pipe, bg, iteration, *, quantize8=True, ms_ssim=True, speculative=True, clamp=False,
+                   times=None, renderer=None):
+    """Render every camera and score it against gts[v] ([3,H,W]) without a host read per view: the frames go through
+    `SpeculativeRenderer`, each frame's metrics call takes that frame's overflow word as `invalid_flag`, and the [V,8] table is read
+    ONCE at the end.  A ring of frames ends in one `flush()`; only if that flush had to re-render frames (their rows are NaN) are
+    the ring's rows looked at, and the NaN ones recomputed from the replaced images.  speculative=False renders every frame with
+    `render()` in its exact mode (one synchronisation inside each).  Returns {"summary": {"SSIM", "PSNR", "MS-SSIM", "D-SSIM",
+    "L1": means over the views, the reference's key names [REF metrics.py:157-162]}, "per_view": the [V,8] float64 device table,
+    "rerendered": frames rendered again}."""
+    table, m, again = _score_views(model, cameras, gts, pipe, bg, iteration, speculative, times, renderer,
+                                   dict(quantize8=quantize8, ms_ssim=ms_ssim, clamp=clamp))
+    summary = {"SSIM": float(m[SSIM]), "PSNR": float(m[PSNR]), "MS-SSIM": float(m[MS_SSIM]), "D-SSIM": float(m[D_SSIM]), "L1": float(m[L1])}
+    return {"summary": summary, "per_view": table, "rerendered": again}
+
+
+def _score_views(model, cameras, gts, pipe, bg, iteration, speculative, times, renderer, kw):
+    """The loop behind evaluate_views / report_views: (the [V,8] device table, its column means from the ONE host read, frames
+    rendered again)."""
+    from .renderer import SpeculativeRenderer, render
+    dev = bg.device
+    V = len(cameras)
+    if len(gts) != V:
+        raise RuntimeError(f"evaluate_views: {V} cameras but {len(gts)} ground-truth images")
+    times = _times(cameras, times, dev)
+    table = torch.full((V, METRIC_COUNT), float("nan"), dtype=torch.float64, device=dev)
+    again = 0
+    with torch.no_grad():
+        if not speculative:
+            for v in range(V):
+                img = render(cameras[v], model, pipe, bg, time=times[v], it=iteration)["render"]
+                image_metrics(img, gts[v], out=table[v:v + 1], **kw)
+        else:
+            sr = renderer if renderer is not None else SpeculativeRenderer(model, pipe, bg)
+            sr.flush()          # (a caller's renderer: its ring starts empty, so ring and rows stay in step)
+            ring = []           # (row, image) of the frames since the last flush
+
+            def close_ring():
+                nonlocal again, ring
+                n = sr.flush()
+                if n:
+                    lo, hi = ring[0][0], ring[-1][0] + 1
+                    bad = torch.isnan(table[lo:hi, L1]).cpu()       # (only after an overflow: the rows to do again)
+                    for row, img in ring:
+                        if bool(bad[row - lo]):
+                            image_metrics(img, gts[row], out=table[row:row + 1], **kw)
+                    again += n
+                ring = []
+
+            for v in range(V):
+                if len(ring) >= sr.slots:
+                    close_ring()
+                img = sr(cameras[v], time=times[v], it=iteration)["render"]
+                st = sr.last_status
+                image_metrics(img, gts[v], out=table[v:v + 1], invalid_flag=None if st is None else st[1:2], **kw)
+                if st is not None:
+                    ring.append((v, img))
+            close_ring()
+    return table, table.cpu().mean(dim=0), again
+
+
+def report_views(model, cameras, gts, pipe, bg, iteration, *, speculative=True, times=None, renderer=None):
+    """The `training_report` form [REF train.py:252-282]: both images clamped to [0, 1], no quantisation, no MS-SSIM; returns
+    {"L1": mean L1, "PSNR": mean over the views of the per-channel-mean PSNR, "per_view": the table}."""
+    table, m, _ = _score_views(model, cameras, gts, pipe, bg, iteration, speculative, times, renderer,
+                               dict(quantize8=False, ms_ssim=False, clamp=True))
+    return {"L1": float(m[L1]), "PSNR": float(m[PSNR_CH]), "per_view": table}
+
+
+def _load_rgb(path, device):
+    """An image file as `to_tensor` gives it: [1,3,H,W] float32 = byte / 255 (true division), first three channels."""
+    from PIL import Image       # (lazy: only the directory form needs it)
+    import numpy as np
+    arr = np.array(Image.open(path))
+    if arr.ndim == 2:
+        arr = arr[:, :, None]
+    t = torch.from_numpy(arr).permute(2, 0, 1)[:3]
+    if t.dtype != torch.uint8:
+        raise RuntimeError(f"evaluate_dirs: {path} is not an 8-bit image")
+    return (t.to(torch.float32) / 255.0)[None].contiguous().to(device)
+
+
+def evaluate_dirs(path, device="cuda", write=True):
+    """The directory form of the reference's metrics.py [REF metrics.py:113-178]: for every `<path>/<method>/` holding `renders/`
+    and `gt/`, score the sorted image pairs (files whose name contains "depth" are skipped), write `<method>/deltas/%05d.jpg` and
+    -- as the reference does -- `<path>/results.json` and `<path>/per_view.json` of the last method.  Keys: SSIM, PSNR, MS-SSIM,
+    D-SSIM.  The reference's two LPIPS keys (LPIPS-vgg, LPIPS-alex) are MISSING: they need pretrained VGG / AlexNet weights this
+    package does not ship.  The images were saved as 8 bits already, so nothing is quantised again.  One table read per method.
+    Returns {method: {"summary": ..., "per_view": ...}} with the dictionaries that were written."""
+    from PIL import Image
+    device = torch.device(device)
+    result = {}
+    for method in sorted(os.listdir(path)):
+        mdir = os.path.join(path, method)
+        rdir, gdir = os.path.join(mdir, "renders"), os.path.join(mdir, "gt")
+        if not (os.path.isdir(rdir) and os.path.isdir(gdir)):
+            continue
+        rnames = [f for f in sorted(os.listdir(rdir)) if "depth" not in f]
+        gnames = sorted(os.listdir(gdir))
+        if len(rnames) != len(gnames) or not rnames:
+            raise RuntimeError(f"evaluate_dirs: {rdir} holds {len(rnames)} images, {gdir} holds {len(gnames)}")
+        table = torch.empty(len(rnames), METRIC_COUNT, dtype=torch.float64, device=device)
+        if write:
+            os.makedirs(os.path.join(mdir, "deltas"), exist_ok=True)
+        pending = []
+        for i, (rn, gn) in enumerate(zip(rnames, gnames)):
+            r = image_metrics(_load_rgb(os.path.join(rdir, rn), device), _load_rgb(os.path.join(gdir, gn), device),
+                              out=table[i:i + 1], deltas=write)
+            if write:
+                pending.append(r.deltas)
+        h = table.cpu()
+        for i, d in enumerate(pending):
+            Image.fromarray(d[0].cpu().numpy()).save(os.path.join(mdir, "deltas", "{0:05d}.jpg".format(i)))
+        cols = {"SSIM": SSIM, "PSNR": PSNR, "MS-SSIM": MS_SSIM, "D-SSIM": D_SSIM}
+        summary = {k: float(h[:, c].mean()) for k, c in cols.items()}
+        per_view = {k: {n: float(h[i, c]) for i, n in enumerate(rnames)} for k, c in cols.items()}
+        result[method] = {"summary": summary, "per_view": per_view}
+        if write:
+            with open(os.path.join(path, "results.json"), "w") as fp:
+                json.dump(summary, fp, indent=True)
+            with open(os.path.join(path, "per_view.json"), "w") as fp:
+                json.dump(per_view, fp, indent=True)
+    return result

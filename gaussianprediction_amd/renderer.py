@@ -170,6 +170,7 @@ class SpeculativeRenderer:
         self._status = None
         self._pending = []          # (slot, camera, time, it, pkg)
         self.rerendered = 0
+        self.last_status = None     # the status words {R, overflow, ...} of the most recent frame (a device view; None after an exact frame)
 
     def _exact(self, viewpoint_camera, time, it):
         """An exact-mode frame (one host synchronisation inside) that reports R and the visible depth keys' range."""
@@ -198,6 +199,7 @@ class SpeculativeRenderer:
             self._status = torch.zeros(self.slots + 1, 8, dtype=torch.int32, device=dev)
             self._key_none = torch.tensor([-1, 0], dtype=torch.int32, device=dev)      # {0xFFFFFFFF, 0}: nothing reported
         if self.capacity <= 0:                      # exact frame: learns R and the key range (the call synchronises anyway)
+            self.last_status = None
             return self._exact(viewpoint_camera, time, it)
         if len(self._pending) >= self.slots:
             self.flush()
@@ -205,6 +207,7 @@ class SpeculativeRenderer:
         pkg = render(viewpoint_camera, self.pc, self.pipe, self.bg, time=time, it=it,
                      binning=(self.capacity, self._status[slot][0:3], self._promise()))
         self._pending.append((slot, viewpoint_camera, time, it, pkg))
+        self.last_status = self._status[slot]
         return pkg
 
     def flush(self):

@@ -569,6 +569,42 @@ int gp_knn_points_backward(int64_t B, int64_t P1, int64_t P2, int32_t D, const f
 int gp_furthest_point_sampling_batched(int32_t b, const int32_t* offset, const int32_t* new_offset, int64_t n_total, int64_t m_total,
                                        const float* xyz, float* tmp, int32_t* idx, gp_stream_t stream);
 
+/* ---- image metrics (csrc/metric_kernels.hip) --------------------------------------------------- */
+/* L1, MSE, PSNR (both call shapes of the reference), SSIM, MS-SSIM and D-SSIM of B image pairs in one call, on the device
+ * [REF metrics.py:138-147, train.py:107,252-282, utils/image_utils.py:18-20, utils/loss_utils.py:54-98].  render / gt: fp32
+ * [B][3][H][W], contiguous.  out[B][GP_METRIC_COUNT] (doubles, device) receives one row per image:
+ *   L1 = mean |a-b|, MSE = mean (a-b)^2, PSNR = 20 log10(1 / sqrt(MSE)) over all three channels (+inf for MSE = 0), PSNR_CH = the
+ *   mean over the channels of the per-channel PSNR, SSIM = the 11 x 11 Gaussian window (sigma 1.5), zero padded, C1 = 0.01^2,
+ *   C2 = 0.03^2, mean over all pixels; MS_SSIM = the five-scale form of pytorch_msssim with data_range 1 (valid convolution, 2 x 2
+ *   average pooling with padding size % 2, ReLU on the terms before the powers 0.0448, 0.2856, 0.3001, 0.2363, 0.1333, mean over the
+ *   channels); D_SSIM = (1 - MS_SSIM) / 2; column 7 is reserved (0).
+ * flags: GP_METRICS_QUANTIZE8 replaces the render, as it is loaded, by floor(x * 255 + 0.5) clamped to [0, 255], divided by 255
+ * (what saving it as an 8-bit image and loading it again does); GP_METRICS_CLAMP01 clamps both images to [0, 1] as they are loaded;
+ * GP_METRICS_MS_SSIM runs the four further pyramid levels -- without it columns 5 and 6 are NaN and levels_out must be NULL; with
+ * it min(H, W) must exceed 160 (the call fails before any launch otherwise).
+ * scratch: gp_image_metrics_scratch_bytes(B, H, W, flags) bytes, 256-byte aligned, uninitialised on entry.  invalid_flag (optional,
+ * one device word per image): non-zero fills that image's row (and its levels_out) with NaN.  levels_out (optional, [B][5][3]): the
+ * mean contrast-structure term of scales 1-4 and the mean SSIM of scale 5 per channel, before the ReLU.  quant_out (optional,
+ * [B][3][H][W] bytes): the 8-bit render (with GP_METRICS_QUANTIZE8 only).  deltas_out (optional, [B][H][W][3] bytes):
+ * trunc(|a - b| * 255) of the images as loaded [REF metrics.py:146-147].
+ * At most six launches whatever B is; per-workgroup double sums in slots of their own, summed in a fixed order: two calls are
+ * bit-identical, and row b of a batched call is bit-identical to a call on image b alone.  No synchronisation. */
+#define GP_METRIC_L1 0
+#define GP_METRIC_MSE 1
+#define GP_METRIC_PSNR 2
+#define GP_METRIC_PSNR_CH 3
+#define GP_METRIC_SSIM 4
+#define GP_METRIC_MS_SSIM 5
+#define GP_METRIC_D_SSIM 6
+#define GP_METRIC_COUNT 8
+#define GP_METRICS_QUANTIZE8 1u
+#define GP_METRICS_CLAMP01 2u
+#define GP_METRICS_MS_SSIM 4u
+int64_t gp_image_metrics_scratch_bytes(int32_t B, int32_t H, int32_t W, uint32_t flags);
+int gp_image_metrics(const float* render, const float* gt, int32_t B, int32_t channels, int32_t H, int32_t W, uint32_t flags,
+                     void* scratch, const uint32_t* invalid_flag, double* out, double* levels_out, uint8_t* quant_out,
+                     uint8_t* deltas_out, gp_stream_t stream);
+
 /* ---- measurement ----------------------------------------------------------------------------- */
 /* gp_profile_enable(level): 0 = off, 1 = bracket only the roofline kernel (composite forward), 2 = every
  * kernel.  When enabled, the library brackets kernels with hipEvent pairs recorded on the launch stream.
@@ -633,8 +669,9 @@ int gp_sh_factor_gradient(int64_t n, int32_t world, const float* factors, int32_
  * gp_adam_step_multi_steps); 5 = round 5 (gp_train_step_run and its three structs);
  * 6 = round 6 (gp_mlp16_pack / gp_mlp16_packed_elems, gp_loss_l1_ssim_fused, gp_sh_factor_gradient; the ReLU words gp_mlp16_forward hands to gp_mlp16_backward changed layout);
  * 7 = round 6, last session (gp_mlp_params.scratch + gp_mlp_scratch_bytes, gp_raster_settings.raw_activations, the saved 16-bit tensors' extent padded to 128 rows);
- * 8 = gp_knn_points, gp_knn_points_backward, gp_furthest_point_sampling_batched (the reference's CUDA-extension shims). */
-#define GP_ABI_VERSION 8
+ * 8 = gp_knn_points, gp_knn_points_backward, gp_furthest_point_sampling_batched (the reference's CUDA-extension shims);
+ * 9 = gp_image_metrics, gp_image_metrics_scratch_bytes. */
+#define GP_ABI_VERSION 9
 int gp_abi_version(void);
 
 #ifdef __cplusplus
