@@ -21,8 +21,6 @@ GP_BUF_GEOM, GP_BUF_BINNING, GP_BUF_IMAGE, GP_BUF_TEMP, GP_BUF_TEMP_DONE = 0, 1,
 
 ALLOC_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_int, C.c_size_t)
 
-_f = C.POINTER(C.c_float)
-
 
 class RasterSettingsC(C.Structure):
     _fields_ = [("image_height", C.c_int32), ("image_width", C.c_int32), ("tanfovx", C.c_float),
@@ -132,21 +130,93 @@ class ProfileEntryC(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_int32), ("total_ms", C.c_float)]
 
 
-EXPORTS = [
-    "gp_raster_forward", "gp_raster_backward", "gp_raster_mark_visible", "gp_raster_debug_binning",
-    "gp_mlp_forward", "gp_mlp_backward", "gp_mlp_pack", "gp_mlp_packed_floats", "gp_mlp_scratch_bytes", "gp_mlp16_forward", "gp_mlp16_backward", "gp_mlp16_pack", "gp_mlp16_packed_elems", "gp_blend_forward", "gp_blend_backward",
-    "gp_activations_forward", "gp_activations_backward", "gp_profile_enable", "gp_profile_collect",
-    "gp_loss_l1_ssim_forward", "gp_loss_l1_ssim_finalize", "gp_loss_l1_ssim_backward", "gp_loss_l1_ssim_fused", "gp_adam_step",
-    "gp_adam_step_multi", "gp_adam_step_multi_steps",
-    "gp_hashgrid_table_entries", "gp_hashgrid_forward", "gp_hashgrid_backward", "gp_knn_keypoints",
-    "gp_weights_forward", "gp_weights_backward", "gp_l1_mean_forward", "gp_l1_mean_backward", "gp_loss_l1_ssim_finalize_reg", "gp_loss_l1_ssim_backward_reg", "gp_furthest_point_sampling", "gp_knn3_mean_dist2",
-    "gp_knn_points", "gp_knn_points_backward", "gp_furthest_point_sampling_batched",
-    "gp_image_metrics", "gp_image_metrics_scratch_bytes",
-    "gp_microbench_copy", "gp_microbench_read", "gp_microbench_mfma", "gp_microbench_valu", "gp_microbench_gather",
-    "gp_debug_option", "gp_debug_counters", "gp_train_step_run", "gp_sh_factor_gradient",
-    "gp_mlp_input_forward", "gp_mlp_input_backward", "gp_linear_forward", "gp_linear_backward", "gp_softmax_forward", "gp_softmax_backward",
-    "gp_last_error", "gp_version", "gp_abi_version",
-]
+class HashGridConfigC(C.Structure):
+    _fields_ = [("n_levels", C.c_int32), ("n_features_per_level", C.c_int32), ("log2_hashmap_size", C.c_int32),
+                ("base_resolution", C.c_int32), ("per_level_scale", C.c_float)]
+
+
+class Ptr:
+    """argtypes class of every pointer parameter that is not a struct of the header (device and host buffers, gp_stream_t,
+    gp_alloc_fn and its context): a tensor stands for its data_ptr(); None, ints of any width, c_void_p, ctypes arrays,
+    byref(...) and function pointers pass as c_void_p takes them."""
+
+    @staticmethod
+    def from_param(obj, _void_p=C.c_void_p, _other=C.c_void_p.from_param):
+        data_ptr = getattr(obj, "data_ptr", None)
+        return _void_p(data_ptr()) if data_ptr is not None else _other(obj)
+
+
+def _prototypes():
+    i32, i64, u32, f32, sz, P, S = C.c_int32, C.c_int64, C.c_uint32, C.c_float, C.c_size_t, Ptr, C.POINTER
+    st, inp, out, saved = S(RasterSettingsC), S(RasterInputsC), S(RasterOutputsC), S(RasterSavedC)
+    mlp, mlp16, mlp_in, mlp_g, cfg = S(MlpParamsC), S(Mlp16ParamsC), S(MlpInputC), S(MlpGradsC), S(HashGridConfigC)
+    return {   # name: (restype, argtypes), as include/gp_hip.h declares them (tests/test_host_and_abi.py compares the two)
+        "gp_raster_forward": (i32, [st, inp, out, saved, P, P, P]),
+        "gp_raster_backward": (i32, [st, inp, out, saved, P, P, S(RasterGradsC), P, P, P]),
+        "gp_raster_mark_visible": (i32, [i64, P, P, P, P]),
+        "gp_raster_debug_binning": (i32, [st, saved, P, P, P]),
+        "gp_mlp_scratch_bytes": (i64, [i64]),
+        "gp_mlp_packed_floats": (i64, [i32]),
+        "gp_mlp_pack": (i32, [mlp, P, P]),
+        "gp_mlp_forward": (i32, [mlp, mlp_in, P, P, P]),
+        "gp_mlp_backward": (i32, [mlp, mlp_in, P, P, mlp_g, P, P, P, P, P]),
+        "gp_mlp_input_forward": (i32, [mlp_in, P, P]),
+        "gp_mlp_input_backward": (i32, [mlp_in, P, P, P, P]),
+        "gp_linear_forward": (i32, [P, i64, i32, P, P, i32, i32, P, P]),
+        "gp_linear_backward": (i32, [P, P, P, i64, i32, P, i32, i32, P, P, P, P]),
+        "gp_softmax_forward": (i32, [P, i64, i32, P, P]),
+        "gp_softmax_backward": (i32, [P, P, i64, i32, P, P]),
+        "gp_mlp16_forward": (i32, [mlp16, mlp_in, P, P, P, P, P]),
+        "gp_mlp16_backward": (i32, [mlp16, mlp_in, P, P, P, P, mlp_g, P, P, P, P, P]),
+        "gp_mlp16_packed_elems": (i64, [i32, i32, i32]),
+        "gp_mlp16_pack": (i32, [mlp, i32, i32, P, P]),
+        "gp_blend_forward": (i32, [S(BlendArgsC), P, P, P]),
+        "gp_blend_backward": (i32, [S(BlendArgsC), P, P, P, P, P, P, P, P, P]),
+        "gp_activations_forward": (i32, [i64, P, P, P, i32, f32, P, P, P]),
+        "gp_activations_backward": (i32, [i64, P, P, P, i32, f32, P, P, P, P, P, P]),
+        "gp_loss_l1_ssim_forward": (i32, [P, P, i32, i32, i32, P, P, P]),
+        "gp_loss_l1_ssim_finalize": (i32, [P, i32, i32, i32, f32, P, P]),
+        "gp_loss_l1_ssim_backward": (i32, [P, P, P, i32, i32, i32, f32, P, P, P]),
+        "gp_loss_l1_ssim_fused": (i32, [P, P, i32, i32, i32, f32, P, P, P, P, i64, f32, P, P]),
+        "gp_loss_l1_ssim_finalize_reg": (i32, [P, i32, i32, i32, f32, P, i64, f32, P, P]),
+        "gp_loss_l1_ssim_backward_reg": (i32, [P, P, P, i32, i32, i32, f32, P, P, P, i64, f32, P, P]),
+        "gp_l1_mean_forward": (i32, [P, i64, f32, P, P, P]),
+        "gp_l1_mean_backward": (i32, [P, i64, f32, P, P, P]),
+        "gp_adam_step": (i32, [P, P, P, P, i64, f32, f32, f32, f32, i64, i32, P]),
+        "gp_adam_step_multi": (i32, [i32, P, P, P, P, P, P, f32, f32, f32, i64, i32, u32, P, P]),
+        "gp_adam_step_multi_steps": (i32, [i32, P, P, P, P, P, P, P, f32, f32, f32, i32, u32, P, P]),
+        "gp_train_step_run": (i32, [S(StepPlanC), S(StepViewC), S(StepUpdateC), P, P, P]),
+        "gp_hashgrid_table_entries": (i64, [cfg]),
+        "gp_hashgrid_forward": (i32, [cfg, i64, P, P, P, P, P]),
+        "gp_hashgrid_backward": (i32, [cfg, i64, P, P, P, P, P]),
+        "gp_weights_forward": (i32, [cfg, i64, P, P, P, i32, P, P, P]),
+        "gp_weights_backward": (i32, [cfg, i64, P, P, P, i32, P, P, P, P, P, P]),
+        "gp_knn_keypoints": (i32, [i64, P, P, i32, f32, i64, P, P, i32, P, P, P, P, P]),
+        "gp_knn3_mean_dist2": (i32, [i64, P, P, P]),
+        "gp_furthest_point_sampling": (i32, [i64, P, i64, P, P, P]),
+        "gp_knn_points": (i32, [i64, i64, i64, i32, P, P, P, P, i32, i32, f32, i32, i64, f32, P, P, P, P, P]),
+        "gp_knn_points_backward": (i32, [i64, i64, i64, i32, P, P, P, P, P, i32, i32, P, P, P, P]),
+        "gp_furthest_point_sampling_batched": (i32, [i32, P, P, i64, i64, P, P, P, P]),
+        "gp_image_metrics_scratch_bytes": (i64, [i32, i32, i32, u32]),
+        "gp_image_metrics": (i32, [P, P, i32, i32, i32, i32, u32, P, P, P, P, P, P, P]),
+        "gp_profile_enable": (i32, [i32]),
+        "gp_profile_collect": (i32, [S(ProfileEntryC), i32, P]),
+        "gp_microbench_copy": (i32, [P, P, sz, P]),
+        "gp_microbench_read": (i32, [P, sz, P, P]),
+        "gp_microbench_mfma": (i32, [i32, i32, P, P, P]),
+        "gp_microbench_valu": (i32, [i32, i32, P, P, P]),
+        "gp_microbench_gather": (i32, [P, i32, i32, P, sz, P, P]),
+        "gp_debug_option": (i32, [i32, i32]),
+        "gp_debug_counters": (i32, [P]),
+        "gp_last_error": (C.c_char_p, []),
+        "gp_version": (C.c_char_p, []),
+        "gp_sh_factor_gradient": (i32, [i64, i32, P, i32, P, P, P]),
+        "gp_abi_version": (i32, []),
+    }
+
+
+PROTOTYPES = _prototypes()
+EXPORTS = list(PROTOTYPES)
 GP_ABI_VERSION = 9         # include/gp_hip.h: the struct layouts / signatures / buffer-size macros this binding was written against
 
 _lib = None
@@ -171,19 +241,11 @@ def lib() -> C.CDLL:
                 "fallback). Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950).")
         l = C.CDLL(LIB_PATH)
-        for name in EXPORTS:
+        for name, (restype, argtypes) in PROTOTYPES.items():
             if not hasattr(l, name):
                 raise GpHipError(f"{LIB_PATH} does not export {name}")
-        l.gp_last_error.restype = C.c_char_p
-        l.gp_version.restype = C.c_char_p
-        for name in EXPORTS:
-            if name not in ("gp_last_error", "gp_version"):
-                getattr(l, name).restype = C.c_int
-        l.gp_hashgrid_table_entries.restype = C.c_int64
-        l.gp_mlp_packed_floats.restype = C.c_int64
-        l.gp_mlp_scratch_bytes.restype = C.c_int64
-        l.gp_mlp16_packed_elems.restype = C.c_int64
-        l.gp_image_metrics_scratch_bytes.restype = C.c_int64
+            fn = getattr(l, name)
+            fn.restype, fn.argtypes = restype, argtypes
         if int(l.gp_abi_version()) != GP_ABI_VERSION:
             raise GpHipError(f"{LIB_PATH} implements ABI {int(l.gp_abi_version())}, this binding is written against ABI "
                              f"{GP_ABI_VERSION} (include/gp_hip.h): rebuild the library (__graft_entry__.build(force=True))")
@@ -285,6 +347,22 @@ class TorchAllocator:
         b = self.bufs[which]
         return b[0] if b else None
 
+    def __enter__(self):
+        """`with TorchAllocator(dev) as alloc:` around a library call that takes `alloc.cb`: the device guard holds inside the
+        block; on leaving it by any path the allocator is released, and an exception caught in the callback is raised in
+        preference to the library's report of the failed allocation (the caller still reads the return code with check())."""
+        self._guard = on_device(self.device)
+        self._guard.__enter__()
+        return self
+
+    def __exit__(self, etype, exc, tb):
+        error = self.error
+        self.release()
+        self._guard.__exit__(etype, exc, tb)
+        if error is not None and (etype is None or issubclass(etype, GpHipError)):
+            raise error
+        return False
+
     def release(self):
         """Break the self -> callback -> bound method -> self cycle so the buffers are freed by
         reference counting right away (not at the next cyclic GC, seconds and gigabytes later)."""
@@ -295,12 +373,12 @@ class TorchAllocator:
 def profile_enable(level) -> None:
     """0/False = off, 1 = only the roofline kernel (composite forward), 2/True = every kernel."""
     level = 2 if level is True else int(level)
-    check(lib().gp_profile_enable(C.c_int(level)), "gp_profile_enable")
+    check(lib().gp_profile_enable(level), "gp_profile_enable")
 
 
 def profile_collect() -> dict:
     """{kernel name: (launches, total_ms)} since the previous collect (waits for the recorded events)."""
     arr = (ProfileEntryC * 64)()
     n = C.c_int(0)
-    check(lib().gp_profile_collect(arr, C.c_int(64), C.byref(n)), "gp_profile_collect")
+    check(lib().gp_profile_collect(arr, 64, C.byref(n)), "gp_profile_collect")
     return {arr[i].name.decode(): (int(arr[i].launches), float(arr[i].total_ms)) for i in range(n.value)}

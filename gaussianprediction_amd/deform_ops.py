@@ -40,7 +40,7 @@ def packed_weights(wb, ws):
         return c[1]
     dev = ws[0].device
     in_dim = ws[0].shape[1]
-    n = int(_lib.lib().gp_mlp_packed_floats(C.c_int32(in_dim)))
+    n = int(_lib.lib().gp_mlp_packed_floats(in_dim))
     if n <= 0:
         return None
     pk = c[1] if (c is not None and c[1].numel() == n and c[1].device == dev) else torch.empty(n, device=dev)
@@ -48,7 +48,7 @@ def packed_weights(wb, ws):
     for l in range(4):
         params.w[l] = ws[l].data_ptr()
     with _lib.on_device(dev):
-        _lib.check(_lib.lib().gp_mlp_pack(C.byref(params), _lib.ptr(pk), _lib.stream_ptr(dev)), "gp_mlp_pack")
+        _lib.check(_lib.lib().gp_mlp_pack(params, pk, _lib.stream_ptr(dev)), "gp_mlp_pack")
     if len(_PACK_CACHE) > 64:
         _PACK_CACHE.clear()
     _PACK_CACHE[id(leaves[0])] = (key, pk)
@@ -68,7 +68,7 @@ def mlp_scratch(dev, rows):
     key = (dev.index if dev.index is not None else torch.cuda.current_device(), int(torch.cuda.current_stream(dev).cuda_stream))
     t = _SCRATCH.get(key)
     if t is None:
-        n = int(_lib.lib().gp_mlp_scratch_bytes(C.c_int64(SPLIT_ROWS)))
+        n = int(_lib.lib().gp_mlp_scratch_bytes(SPLIT_ROWS))
         if n <= 0:
             return None
         t = torch.zeros((n + 3) // 4, dtype=torch.int32, device=dev)
@@ -121,7 +121,7 @@ class FusedMlp(torch.autograd.Function):
         inp = _lib.MlpInputC(rows, fd, int(xyz_freq), int(time_freq), feature_c.data_ptr(),
                              xyz_c.data_ptr() if xyz_c is not None else None, t_c.data_ptr() if t_c is not None else None)
         with _lib.on_device(dev):
-            rc = _lib.lib().gp_mlp_forward(C.byref(params), C.byref(inp), _lib.ptr(out), _lib.ptr(acts), _lib.stream_ptr(dev))
+            rc = _lib.lib().gp_mlp_forward(params, inp, out, acts, _lib.stream_ptr(dev))
             _lib.check(rc, "gp_mlp_forward")
         if need_grad:
             ctx.save_for_backward(feature_c, xyz_c if xyz_c is not None else torch.empty(0, device=dev),
@@ -175,15 +175,8 @@ class FusedMlp(torch.autograd.Function):
         x_sink = _input_sink(x_leaf, (rows, 3)) if (need_x and has_xyz and xyz_freq > 0) else None
         g_feat = f_sink if f_sink is not None else (torch.empty(rows, fd, device=dev) if need_f else None)
         g_xyz = x_sink if x_sink is not None else (torch.empty(rows, 3, device=dev) if (need_x and has_xyz and xyz_freq > 0) else None)
-        alloc = _lib.TorchAllocator(dev)
-        with _lib.on_device(dev):
-            rc = _lib.lib().gp_mlp_backward(C.byref(params), C.byref(inp), _lib.ptr(acts), _lib.ptr(g), C.byref(grads),
-                                            _lib.ptr(g_feat), _lib.ptr(g_xyz), alloc.cb, None, _lib.stream_ptr(dev))
-            if alloc.error is not None:
-                err = alloc.error
-                alloc.release()
-                raise err
-            alloc.release()
+        with _lib.TorchAllocator(dev) as alloc:
+            rc = _lib.lib().gp_mlp_backward(params, inp, acts, g, grads, g_feat, g_xyz, alloc.cb, None, _lib.stream_ptr(dev))
             _lib.check(rc, "gp_mlp_backward")
         wb_grads = []
         for l in range(5):
@@ -243,7 +236,7 @@ def packed_w16(ws, tdt, cdt, transposed):
     in_dim, out_dim = ws[0].shape[1], ws[4].shape[0]
     ns = 2 if cdt == _lib.GP_DTYPE_F16_SPLIT else 1
     L = _lib.lib()
-    sizes = [ns * int(L.gp_mlp16_packed_elems(C.c_int32(l), C.c_int32(in_dim), C.c_int32(1 if transposed else 0))) for l in range(5)]
+    sizes = [ns * int(L.gp_mlp16_packed_elems(l, in_dim, 1 if transposed else 0)) for l in range(5)]
     offs = [0]
     for n in sizes:
         offs.append(offs[-1] + (n + 127) // 128 * 128)          # 256-byte aligned pieces
@@ -253,7 +246,7 @@ def packed_w16(ws, tdt, cdt, transposed):
         params.w[l] = ws[l].data_ptr()
     ptrs = (C.c_void_p * 5)(*[buf.data_ptr() + 2 * offs[l] for l in range(5)])
     with _lib.on_device(dev):
-        _lib.check(L.gp_mlp16_pack(C.byref(params), C.c_int32(cdt), C.c_int32(1 if transposed else 0), ptrs, _lib.stream_ptr(dev)), "gp_mlp16_pack")
+        _lib.check(L.gp_mlp16_pack(params, cdt, 1 if transposed else 0, ptrs, _lib.stream_ptr(dev)), "gp_mlp16_pack")
     return buf, [int(ptrs[l]) for l in range(5)]
 
 
@@ -296,8 +289,7 @@ class FusedMlp16(torch.autograd.Function):
         inp = _lib.MlpInputC(rows, fd, int(xyz_freq), int(time_freq), feature_c.data_ptr(),
                              xyz_c.data_ptr() if xyz_c is not None else None, t_c.data_ptr() if t_c is not None else None)
         with _lib.on_device(dev):
-            rc = _lib.lib().gp_mlp16_forward(C.byref(params), C.byref(inp), _lib.ptr(out), _lib.ptr(xT), _lib.ptr(hT), _lib.ptr(masks),
-                                             _lib.stream_ptr(dev))
+            rc = _lib.lib().gp_mlp16_forward(params, inp, out, xT, hT, masks, _lib.stream_ptr(dev))
             _lib.check(rc, "gp_mlp16_forward")
         if need_grad:
             e = torch.empty(0, device=dev)
@@ -339,15 +331,9 @@ class FusedMlp16(torch.autograd.Function):
         need_f, need_x = ctx.needs
         g_feat = torch.empty(rows, fd, device=dev) if need_f else None
         g_xyz = torch.empty(rows, 3, device=dev) if (need_x and has_xyz and xyz_freq > 0) else None
-        alloc = _lib.TorchAllocator(dev)
-        with _lib.on_device(dev):
-            rc = _lib.lib().gp_mlp16_backward(C.byref(params), C.byref(inp), _lib.ptr(xT), _lib.ptr(hT), _lib.ptr(masks), _lib.ptr(g),
-                                              C.byref(grads), _lib.ptr(g_feat), _lib.ptr(g_xyz), alloc.cb, None, _lib.stream_ptr(dev))
-            if alloc.error is not None:
-                err = alloc.error
-                alloc.release()
-                raise err
-            alloc.release()
+        with _lib.TorchAllocator(dev) as alloc:
+            rc = _lib.lib().gp_mlp16_backward(params, inp, xT, hT, masks, g, grads, g_feat, g_xyz, alloc.cb, None,
+                                              _lib.stream_ptr(dev))
             _lib.check(rc, "gp_mlp16_backward")
         wb_grads = []
         for l in range(5):
@@ -411,7 +397,7 @@ class KeypointBlend(torch.autograd.Function):
         xyz_t = torch.empty(N, 3, device=dev)
         q_t = torch.empty(N, 4, device=dev)
         with _lib.on_device(dev):
-            rc = _lib.lib().gp_blend_forward(C.byref(args), _lib.ptr(xyz_t), _lib.ptr(q_t), _lib.stream_ptr(dev))
+            rc = _lib.lib().gp_blend_forward(args, xyz_t, q_t, _lib.stream_ptr(dev))
             _lib.check(rc, "gp_blend_forward")
         e = torch.empty(0, device=dev)
         ctx.save_for_backward(delta_c, raw_c if raw_c is not None else e,
@@ -438,15 +424,8 @@ class KeypointBlend(torch.autograd.Function):
         sinks = [_overwrite_sink(t_) for t_ in ctx.leaves]
         g_xyz = sinks[0] if sinks[0] is not None else torch.empty(N, 3, device=dev)
         g_rot = sinks[1] if sinks[1] is not None else torch.empty(N, 4, device=dev)
-        alloc = _lib.TorchAllocator(dev)
-        with _lib.on_device(dev):
-            rc = _lib.lib().gp_blend_backward(C.byref(args), _lib.ptr(gx), _lib.ptr(gq), _lib.ptr(g_delta), _lib.ptr(g_raw),
-                                              _lib.ptr(g_xyz), _lib.ptr(g_rot), alloc.cb, None, _lib.stream_ptr(dev))
-            if alloc.error is not None:
-                err = alloc.error
-                alloc.release()
-                raise err
-            alloc.release()
+        with _lib.TorchAllocator(dev) as alloc:
+            rc = _lib.lib().gp_blend_backward(args, gx, gq, g_delta, g_raw, g_xyz, g_rot, alloc.cb, None, _lib.stream_ptr(dev))
             _lib.check(rc, "gp_blend_backward")
         for t_, sk in zip(ctx.leaves, sinks):
             if sk is not None:
@@ -467,11 +446,9 @@ class Activations(torch.autograd.Function):
         stride = d_c.shape[1] if d_c is not None else 0
         scale = torch.empty(N, 3, device=dev)
         opacity = torch.empty(N, 1, device=dev)
-        dptr = C.c_void_p(d_c.data_ptr() + 4 * int(col)) if d_c is not None else None
+        dptr = d_c.data_ptr() + 4 * int(col) if d_c is not None else None
         with _lib.on_device(dev):
-            rc = _lib.lib().gp_activations_forward(C.c_int64(N), _lib.ptr(s_c), _lib.ptr(o_c), dptr, C.c_int32(stride),
-                                                   C.c_float(float(beta)), _lib.ptr(scale), _lib.ptr(opacity),
-                                                   _lib.stream_ptr(dev))
+            rc = _lib.lib().gp_activations_forward(N, s_c, o_c, dptr, stride, float(beta), scale, opacity, _lib.stream_ptr(dev))
             _lib.check(rc, "gp_activations_forward")
         ctx.save_for_backward(s_c, o_c, d_c if d_c is not None else torch.empty(0, device=dev))
         ctx.meta = (int(col), float(beta), d_c is not None)
@@ -491,12 +468,11 @@ class Activations(torch.autograd.Function):
         g_oraw = sinks[1] if sinks[1] is not None else torch.empty(N, 1, device=dev)
         g_delta = torch.zeros_like(d_c) if has_d else None
         stride = d_c.shape[1] if has_d else 0
-        dptr = C.c_void_p(d_c.data_ptr() + 4 * col) if has_d else None
-        gdptr = C.c_void_p(g_delta.data_ptr() + 4 * col) if has_d else None
+        dptr = d_c.data_ptr() + 4 * col if has_d else None
+        gdptr = g_delta.data_ptr() + 4 * col if has_d else None
         with _lib.on_device(dev):
-            rc = _lib.lib().gp_activations_backward(C.c_int64(N), _lib.ptr(s_c), _lib.ptr(o_c), dptr, C.c_int32(stride),
-                                                    C.c_float(beta), _lib.ptr(gs), _lib.ptr(go), _lib.ptr(g_sraw),
-                                                    _lib.ptr(g_oraw), gdptr, _lib.stream_ptr(dev))
+            rc = _lib.lib().gp_activations_backward(N, s_c, o_c, dptr, stride, beta, gs, go, g_sraw, g_oraw, gdptr,
+                                                    _lib.stream_ptr(dev))
             _lib.check(rc, "gp_activations_backward")
         for t_, sk in zip(ctx.leaves, sinks):
             if sk is not None:
@@ -521,7 +497,7 @@ class MlpInput(torch.autograd.Function):
         inp = _lib.MlpInputC(rows, fd, xf, tf, f_c.data_ptr(), x_c.data_ptr() if x_c is not None else None,
                              t_c.data_ptr() if t_c is not None else None)
         with _lib.on_device(dev):
-            _lib.check(_lib.lib().gp_mlp_input_forward(C.byref(inp), _lib.ptr(out), _lib.stream_ptr(dev)), "gp_mlp_input_forward")
+            _lib.check(_lib.lib().gp_mlp_input_forward(inp, out, _lib.stream_ptr(dev)), "gp_mlp_input_forward")
         ctx.save_for_backward(x_c if x_c is not None else torch.empty(0, device=dev))
         ctx.meta = (rows, fd, xf, tf, feature.requires_grad, xyz is not None and torch.is_tensor(xyz) and xyz.requires_grad and xf > 0)
         return out
@@ -537,7 +513,7 @@ class MlpInput(torch.autograd.Function):
         if need_f or need_x:
             inp = _lib.MlpInputC(rows, fd, xf, tf, None, x_c.data_ptr() if xf > 0 else None, None)
             with _lib.on_device(dev):
-                _lib.check(_lib.lib().gp_mlp_input_backward(C.byref(inp), _lib.ptr(g), _lib.ptr(d_f), _lib.ptr(d_x), _lib.stream_ptr(dev)),
+                _lib.check(_lib.lib().gp_mlp_input_backward(inp, g, d_f, d_x, _lib.stream_ptr(dev)),
                            "gp_mlp_input_backward")
         return d_f, d_x, None, None, None
 
@@ -563,13 +539,13 @@ class GenericMlp(torch.autograd.Function):
                 if w.shape[1] != acts[-1].shape[1]:
                     raise RuntimeError(f"GenericMlp: layer {l} takes {w.shape[1]} inputs, got {acts[-1].shape[1]}")
                 y = torch.empty(rows, w.shape[0], device=dev)
-                _lib.check(L.gp_linear_forward(_lib.ptr(acts[-1]), C.c_int64(rows), C.c_int32(w.shape[1]), _lib.ptr(w), _lib.ptr(b),
-                                               C.c_int32(w.shape[0]), C.c_int32(1 if l < len(ws) - 1 else 0), _lib.ptr(y), st), "gp_linear_forward")
+                _lib.check(L.gp_linear_forward(acts[-1], rows, w.shape[1], w, b, w.shape[0], 1 if l < len(ws) - 1 else 0, y, st),
+                           "gp_linear_forward")
                 acts.append(y)
             out = acts[-1]
             if use_softmax:
                 out = torch.empty_like(acts[-1])
-                _lib.check(L.gp_softmax_forward(_lib.ptr(acts[-1]), C.c_int64(rows), C.c_int32(out.shape[1]), _lib.ptr(out), st), "gp_softmax_forward")
+                _lib.check(L.gp_softmax_forward(acts[-1], rows, out.shape[1], out, st), "gp_softmax_forward")
         need = x.requires_grad or any(t.requires_grad for t in wb)
         if need:
             ctx.save_for_backward(out if use_softmax else torch.empty(0, device=dev), *acts[:-1], *ws)
@@ -590,7 +566,7 @@ class GenericMlp(torch.autograd.Function):
             st = _lib.stream_ptr(dev)
             if use_softmax:
                 g2 = torch.empty_like(g)
-                _lib.check(L.gp_softmax_backward(_lib.ptr(sm), _lib.ptr(g), C.c_int64(rows), C.c_int32(g.shape[1]), _lib.ptr(g2), st), "gp_softmax_backward")
+                _lib.check(L.gp_softmax_backward(sm, g, rows, g.shape[1], g2, st), "gp_softmax_backward")
                 g = g2
             for l in range(n - 1, -1, -1):
                 w = ws[l]
@@ -599,8 +575,8 @@ class GenericMlp(torch.autograd.Function):
                 y = acts[l + 1] if relu else None
                 dw, db = torch.zeros_like(w), torch.zeros(w.shape[0], device=dev)
                 dx = torch.empty(rows, w.shape[1], device=dev) if (l > 0 or need_x) else None
-                _lib.check(L.gp_linear_backward(_lib.ptr(acts[l]), _lib.ptr(y), _lib.ptr(g), C.c_int64(rows), C.c_int32(w.shape[1]), _lib.ptr(w),
-                                                C.c_int32(w.shape[0]), C.c_int32(relu), _lib.ptr(dx), _lib.ptr(dw), _lib.ptr(db), st), "gp_linear_backward")
+                _lib.check(L.gp_linear_backward(acts[l], y, g, rows, w.shape[1], w, w.shape[0], relu, dx, dw, db, st),
+                           "gp_linear_backward")
                 grads[2 * l], grads[2 * l + 1] = dw, db
                 g = dx
         return (g if need_x else None, None, *grads)

@@ -351,12 +351,11 @@ def sh_factor_gradient(factors: torch.Tensor, degree: int, g_dc: torch.Tensor, g
     order) of the rank-one SH gradients (gp_sh_factor_gradient)."""
     world, n, _ = factors.shape
     if factors.is_cuda:
-        import ctypes as C
         from . import _lib
         assert factors.is_contiguous() and g_dc.is_contiguous() and g_rest.is_contiguous() and factors.dtype == torch.float32
         with _lib.on_device(factors.device):
-            _lib.check(_lib.lib().gp_sh_factor_gradient(C.c_int64(n), C.c_int32(world), _lib.ptr(factors), C.c_int32(int(degree)), _lib.ptr(g_dc),
-                                                        _lib.ptr(g_rest), _lib.stream_ptr(factors.device)), "gp_sh_factor_gradient")
+            _lib.check(_lib.lib().gp_sh_factor_gradient(n, world, factors, int(degree), g_dc, g_rest, _lib.stream_ptr(factors.device)),
+                       "gp_sh_factor_gradient")
         return
     if host_sh_factor_gradient is None:
         raise RuntimeError("sh_factor_gradient: CPU tensors have no implementation (the HIP library is the only one)")

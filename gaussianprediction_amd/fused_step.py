@@ -295,18 +295,12 @@ class FusedStage3:
         P = self.plan
         P.sh_degree = int(pc.active_sh_degree)
         P.reg_scale = 1.0e-5 if ts.iteration >= pc.args.jointly_iteration else 0.0       # [REF scene/gaussian_model.py:174-178]
-        alloc = _lib.TorchAllocator(self.dev)
-        with _lib.on_device(self.dev):
-            try:
-                rc = _lib.lib().gp_train_step_run(C.byref(P), C.byref(v), C.byref(u), alloc.cb, None, _lib.stream_ptr(self.dev))
-                if self._hook_error is not None:
-                    err, self._hook_error = self._hook_error, None
-                    raise err
-                if alloc.error is not None:
-                    raise alloc.error
-                _lib.check(rc, "gp_train_step_run")
-            finally:
-                alloc.release()
+        with _lib.TorchAllocator(self.dev) as alloc:
+            rc = _lib.lib().gp_train_step_run(P, v, u, alloc.cb, None, _lib.stream_ptr(self.dev))
+            if self._hook_error is not None:
+                err, self._hook_error = self._hook_error, None
+                raise err
+            _lib.check(rc, "gp_train_step_run")
         # ---- what FusedAdam.step does around its launch
         excluded = sh_pair if fuse is not None else (tuple(ts._chained_params) if chained else None)
         opt.external_step(keep_grad=keep, exclude=excluded)

@@ -9,7 +9,6 @@ HIP only: there is no CPU fallback.
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 
 import torch
@@ -36,17 +35,10 @@ def _forward(p1, p2, l1, l2, K, norm, r2_max, splits, pad_idx, pad_dist):
     P2 = p2.shape[1]
     dists = torch.empty(B, P1, K, device=p1.device)
     idx = torch.empty(B, P1, K, dtype=torch.int64, device=p1.device)
-    alloc = _lib.TorchAllocator(p1.device)
-    with _lib.on_device(p1.device):
-        rc = _lib.lib().gp_knn_points(C.c_int64(B), C.c_int64(P1), C.c_int64(P2), C.c_int32(D), _lib.ptr(p1), _lib.ptr(p2), _lib.ptr(l1),
-                                      _lib.ptr(l2), C.c_int32(K), C.c_int32(norm), C.c_float(r2_max), C.c_int32(splits),
-                                      C.c_int64(pad_idx), C.c_float(pad_dist), _lib.ptr(dists), _lib.ptr(idx), alloc.cb, None,
-                                      _lib.stream_ptr(p1.device))
-    err = alloc.error
-    alloc.release()
-    if err is not None:
-        raise err
-    _lib.check(rc, "gp_knn_points")
+    with _lib.TorchAllocator(p1.device) as alloc:
+        rc = _lib.lib().gp_knn_points(B, P1, P2, D, p1, p2, l1, l2, K, norm, r2_max, splits, pad_idx, pad_dist, dists, idx,
+                                      alloc.cb, None, _lib.stream_ptr(p1.device))
+        _lib.check(rc, "gp_knn_points")
     return dists, idx
 
 
@@ -76,10 +68,8 @@ class _KnnPoints(torch.autograd.Function):
         g1 = torch.zeros_like(x1) if ctx.needs_input_grad[0] else None
         g2 = torch.zeros_like(x2) if ctx.needs_input_grad[1] else None
         with _lib.on_device(x1.device):
-            _lib.check(_lib.lib().gp_knn_points_backward(C.c_int64(B), C.c_int64(P1), C.c_int64(x2.shape[1]), C.c_int32(D), _lib.ptr(x1),
-                                                         _lib.ptr(x2), _lib.ptr(l1), _lib.ptr(l2), _lib.ptr(idx), C.c_int32(idx.shape[2]),
-                                                         C.c_int32(ctx.norm), _lib.ptr(g), _lib.ptr(g1), _lib.ptr(g2),
-                                                         _lib.stream_ptr(x1.device)), "gp_knn_points_backward")
+            _lib.check(_lib.lib().gp_knn_points_backward(B, P1, x2.shape[1], D, x1, x2, l1, l2, idx, idx.shape[2], ctx.norm, g,
+                                                         g1, g2, _lib.stream_ptr(x1.device)), "gp_knn_points_backward")
         return g1, g2, None, None, None, None, None, None, None, None
 
 
@@ -120,7 +110,6 @@ def furthest_point_sampling_batched(xyz, offset, new_offset, tmp=None, idx=None)
     if tmp is None or tmp.dtype != torch.float32 or tmp.numel() < x.shape[0] or not tmp.is_contiguous():
         tmp = torch.empty(x.shape[0], device=x.device)
     with _lib.on_device(x.device):
-        _lib.check(_lib.lib().gp_furthest_point_sampling_batched(C.c_int32(b), _lib.ptr(off), _lib.ptr(noff), C.c_int64(x.shape[0]),
-                                                                 C.c_int64(idx.numel()), _lib.ptr(x), _lib.ptr(tmp), _lib.ptr(idx),
+        _lib.check(_lib.lib().gp_furthest_point_sampling_batched(b, off, noff, x.shape[0], idx.numel(), x, tmp, idx,
                                                                  _lib.stream_ptr(x.device)), "gp_furthest_point_sampling_batched")
     return idx

@@ -31,20 +31,17 @@ class L1SSIMLoss(torch.autograd.Function):
         need = image.requires_grad or (reg_x is not None and reg_x.requires_grad)
         dmaps = torch.empty(3, 3, H, W, device=dev) if need else None
         with _lib.on_device(dev):
-            rc = _lib.lib().gp_loss_l1_ssim_forward(_lib.ptr(img), _lib.ptr(g), C.c_int32(3), C.c_int32(H), C.c_int32(W),
-                                                    _lib.ptr(sums), _lib.ptr(dmaps), _lib.stream_ptr(dev))
+            rc = _lib.lib().gp_loss_l1_ssim_forward(img, g, 3, H, W, sums, dmaps, _lib.stream_ptr(dev))
             _lib.check(rc, "gp_loss_l1_ssim_forward")
         lam = float(lambda_dssim)
         loss_t = torch.empty(1, dtype=torch.float32, device=dev)
         xc = reg_x.detach().to(torch.float32).contiguous() if reg_x is not None else None
         with _lib.on_device(dev):
             if xc is None:
-                rc = _lib.lib().gp_loss_l1_ssim_finalize(_lib.ptr(sums), C.c_int32(3), C.c_int32(H), C.c_int32(W), C.c_float(lam),
-                                                         _lib.ptr(loss_t), _lib.stream_ptr(dev))
+                rc = _lib.lib().gp_loss_l1_ssim_finalize(sums, 3, H, W, lam, loss_t, _lib.stream_ptr(dev))
             else:
-                rc = _lib.lib().gp_loss_l1_ssim_finalize_reg(_lib.ptr(sums), C.c_int32(3), C.c_int32(H), C.c_int32(W), C.c_float(lam),
-                                                             _lib.ptr(xc), C.c_int64(xc.numel()), C.c_float(float(reg_scale)),
-                                                             _lib.ptr(loss_t), _lib.stream_ptr(dev))
+                rc = _lib.lib().gp_loss_l1_ssim_finalize_reg(sums, 3, H, W, lam, xc, xc.numel(), float(reg_scale), loss_t,
+                                                             _lib.stream_ptr(dev))
             _lib.check(rc, "gp_loss_l1_ssim_finalize")
         loss = loss_t.reshape(())
         if need:
@@ -63,18 +60,14 @@ class L1SSIMLoss(torch.autograd.Function):
         gx = None
         with _lib.on_device(dev):
             if ctx.reg is None:
-                rc = _lib.lib().gp_loss_l1_ssim_backward(_lib.ptr(img), _lib.ptr(g), _lib.ptr(dmaps), C.c_int32(3), C.c_int32(H),
-                                                         C.c_int32(W), C.c_float(ctx.lam), _lib.ptr(up), _lib.ptr(dimg),
-                                                         _lib.stream_ptr(dev))
+                rc = _lib.lib().gp_loss_l1_ssim_backward(img, g, dmaps, 3, H, W, ctx.lam, up, dimg, _lib.stream_ptr(dev))
             else:
                 # (a leaf whose .grad buffer is marked fresh takes the regulariser's gradient directly: deform_ops._input_sink)
                 from .deform_ops import _input_sink
                 sink = _input_sink(getattr(ctx, "reg_leaf", None), ctx.reg[1]) if xc.is_contiguous() else None
                 gx = sink if sink is not None else torch.empty_like(xc)
-                rc = _lib.lib().gp_loss_l1_ssim_backward_reg(_lib.ptr(img), _lib.ptr(g), _lib.ptr(dmaps), C.c_int32(3), C.c_int32(H),
-                                                             C.c_int32(W), C.c_float(ctx.lam), _lib.ptr(up), _lib.ptr(dimg), _lib.ptr(xc),
-                                                             C.c_int64(xc.numel()), C.c_float(ctx.reg[0]), _lib.ptr(gx),
-                                                             _lib.stream_ptr(dev))
+                rc = _lib.lib().gp_loss_l1_ssim_backward_reg(img, g, dmaps, 3, H, W, ctx.lam, up, dimg, xc, xc.numel(), ctx.reg[0],
+                                                             gx, _lib.stream_ptr(dev))
                 gx = gx.reshape(ctx.reg[1])
                 if sink is not None:
                     from . import grad_sink
@@ -96,8 +89,8 @@ class _AddL1Mean(torch.autograd.Function):
         base = loss.detach().to(torch.float32).reshape(1).contiguous()
         out = torch.empty(1, device=xc.device)
         with _lib.on_device(xc.device):
-            _lib.check(_lib.lib().gp_l1_mean_forward(_lib.ptr(xc), C.c_int64(xc.numel()), C.c_float(scale), _lib.ptr(base),
-                                                     _lib.ptr(out), _lib.stream_ptr(xc.device)), "gp_l1_mean_forward")
+            _lib.check(_lib.lib().gp_l1_mean_forward(xc, xc.numel(), scale, base, out, _lib.stream_ptr(xc.device)),
+                       "gp_l1_mean_forward")
         ctx.save_for_backward(xc)
         ctx.scale, ctx.shape = float(scale), x.shape
         return out.reshape(loss.shape)
@@ -108,8 +101,8 @@ class _AddL1Mean(torch.autograd.Function):
         up = g.detach().to(torch.float32).reshape(1).contiguous()
         gx = torch.empty_like(xc)
         with _lib.on_device(xc.device):
-            _lib.check(_lib.lib().gp_l1_mean_backward(_lib.ptr(xc), C.c_int64(xc.numel()), C.c_float(ctx.scale), _lib.ptr(up),
-                                                      _lib.ptr(gx), _lib.stream_ptr(xc.device)), "gp_l1_mean_backward")
+            _lib.check(_lib.lib().gp_l1_mean_backward(xc, xc.numel(), ctx.scale, up, gx, _lib.stream_ptr(xc.device)),
+                       "gp_l1_mean_backward")
         return g, gx.reshape(ctx.shape), None
 
 
@@ -336,16 +329,14 @@ class FusedAdam:
                     mask |= 1 << k
         b1, b2 = self.betas
         dev = self.bucket.flat.device
-        sp = _lib.stream_ptr(dev) if stream is None else C.c_void_p(stream.cuda_stream)
+        sp = _lib.stream_ptr(dev) if stream is None else stream.cuda_stream
         with _lib.on_device(dev):
             if STEPS is None:
-                rc = _lib.lib().gp_adam_step_multi(C.c_int32(n), P, G, M, V, NUM, LR, C.c_float(b1), C.c_float(b2), C.c_float(self.eps),
-                                                   C.c_int64(step_no), C.c_int32(1 if zero_grad else 0), C.c_uint32(mask),
-                                                   _lib.ptr(skip_flag), sp)
+                rc = _lib.lib().gp_adam_step_multi(n, P, G, M, V, NUM, LR, b1, b2, self.eps, step_no, 1 if zero_grad else 0, mask,
+                                                   skip_flag, sp)
             else:
-                rc = _lib.lib().gp_adam_step_multi_steps(C.c_int32(n), P, G, M, V, NUM, LR, STEPS, C.c_float(b1), C.c_float(b2),
-                                                         C.c_float(self.eps), C.c_int32(1 if zero_grad else 0), C.c_uint32(mask),
-                                                         _lib.ptr(skip_flag), sp)
+                rc = _lib.lib().gp_adam_step_multi_steps(n, P, G, M, V, NUM, LR, STEPS, b1, b2, self.eps, 1 if zero_grad else 0, mask,
+                                                         skip_flag, sp)
             _lib.check(rc, "gp_adam_step_multi")
 
     def step(self, zero_grad=True, keep_grad=(), skip_flag=None, only=None, exclude=None, stream=None, advance=True, hold=(), fresh_grad=()):

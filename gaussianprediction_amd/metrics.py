@@ -11,7 +11,6 @@ unpinned (the definition is restated in include/gp_hip.h and checked against a f
 LPIPS is not provided: it needs pretrained network weights this package does not ship.  HIP only: CPU tensors raise."""
 from __future__ import annotations
 
-import ctypes as C
 import json
 import os
 from types import SimpleNamespace
@@ -33,7 +32,7 @@ def metrics_scratch(device, B, H, W, flags):
     key = (device.index, _lib.stream_ptr(device).value, B, H, W, flags)
     t = _scratch.get(key)
     if t is None:
-        n = int(_lib.lib().gp_image_metrics_scratch_bytes(C.c_int32(B), C.c_int32(H), C.c_int32(W), C.c_uint32(flags)))
+        n = int(_lib.lib().gp_image_metrics_scratch_bytes(B, H, W, flags))
         if n < 0:
             raise _lib.GpHipError(f"gp_image_metrics_scratch_bytes: {_lib.lib().gp_last_error().decode(errors='replace')}")
         t = torch.empty(n + 256, dtype=torch.uint8, device=device)
@@ -92,9 +91,7 @@ def image_metrics(render, gt, *, quantize8=False, clamp=False, ms_ssim=True, out
     with _lib.on_device(dev):
         scratch = metrics_scratch(dev, B, H, W, flags)
         sp = (scratch.data_ptr() + 255) & ~255
-        rc = _lib.lib().gp_image_metrics(_lib.ptr(a), _lib.ptr(b), C.c_int32(B), C.c_int32(3), C.c_int32(H), C.c_int32(W), C.c_uint32(flags),
-                                         C.c_void_p(sp), _lib.ptr(invalid_flag), _lib.ptr(table), _lib.ptr(lv), _lib.ptr(qo), _lib.ptr(do),
-                                         _lib.stream_ptr(dev))
+        rc = _lib.lib().gp_image_metrics(a, b, B, 3, H, W, flags, sp, invalid_flag, table, lv, qo, do, _lib.stream_ptr(dev))
         _lib.check(rc, "gp_image_metrics")
     return SimpleNamespace(table=table, names=NAMES, levels=lv, quantized=qo, deltas=do)
 

@@ -23,11 +23,10 @@ def measure(device="cuda:0", gib=1.0, reps=10, mfma_iters=4096) -> dict:
     st = _lib.stream_ptr(dev)
 
     def run():
-        _lib.check(L.gp_microbench_copy(_lib.ptr(dst), _lib.ptr(src), C.c_size_t(nbytes), st), "gp_microbench_copy")
-        _lib.check(L.gp_microbench_read(_lib.ptr(src), C.c_size_t(nbytes), _lib.ptr(sink), st), "gp_microbench_read")
+        _lib.check(L.gp_microbench_copy(dst, src, nbytes, st), "gp_microbench_copy")
+        _lib.check(L.gp_microbench_read(src, nbytes, sink, st), "gp_microbench_read")
         for dt in (0, 1, 2):
-            _lib.check(L.gp_microbench_mfma(C.c_int(dt), C.c_int(mfma_iters), _lib.ptr(sink), C.byref(flop), st),
-                       "gp_microbench_mfma")
+            _lib.check(L.gp_microbench_mfma(dt, mfma_iters, sink, C.byref(flop), st), "gp_microbench_mfma")
             flops[dt] = flop.value
 
     flops = {}

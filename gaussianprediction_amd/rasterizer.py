@@ -144,24 +144,16 @@ class _RasterizeGaussians(torch.autograd.Function):
                 raise RuntimeError("visible_out: contiguous uint8 tensor of N elements on the render device expected")
             out = _lib.RasterOutputsC(_lib.ptr(color), _lib.ptr(radii), _lib.ptr(depth), _lib.ptr(tidx), _lib.ptr(vis))
             saved = _lib.RasterSavedC()
-            alloc = _lib.TorchAllocator(device)
-            try:
-                rc = L.gp_raster_forward(C.byref(st), C.byref(inp), C.byref(out), C.byref(saved), alloc.cb, None,
-                                         _lib.stream_ptr(device))
-                if alloc.error is not None:
-                    raise alloc.error
+            with _lib.TorchAllocator(device) as alloc:
+                rc = L.gp_raster_forward(st, inp, out, saved, alloc.cb, None, _lib.stream_ptr(device))
                 _lib.check(rc, "gp_raster_forward")
-            except BaseException:
-                alloc.release()          # (breaks the allocator's self-reference: the buffers are freed now, not at the next GC)
-                raise
+                geom, binning, image = alloc.first(_lib.GP_BUF_GEOM), alloc.first(_lib.GP_BUF_BINNING), alloc.first(_lib.GP_BUF_IMAGE)
         ctx.set_materialize_grads(False)      # an unused `depth` output must arrive as None, not as zeros
         ctx.sh_leaves = (sh, sh_rest)         # (leaf Parameters: candidates for direct gradient sinks)
         ctx.raster_settings = rs
         ctx.num_rendered = int(saved.num_rendered)
         ctx.sh_coeffs = sh_coeffs
         ctx.flags = (shs is not None, cols is not None, scl is not None, cov is not None, shs_r is not None)
-        geom, binning, image = alloc.first(_lib.GP_BUF_GEOM), alloc.first(_lib.GP_BUF_BINNING), alloc.first(_lib.GP_BUF_IMAGE)
-        alloc.release()
         empty = torch.empty(0, device=device)
         ctx.save_for_backward(m3, shs if shs is not None else empty, shs_r if shs_r is not None else empty,
                               cols if cols is not None else empty, ops,
@@ -239,15 +231,9 @@ class _RasterizeGaussians(torch.autograd.Function):
             grads = _lib.RasterGradsC(_lib.ptr(g_m3), _lib.ptr(g_m2), _lib.ptr(g_sh), _lib.ptr(g_shr), _lib.ptr(g_col), _lib.ptr(g_op),
                                       _lib.ptr(g_scl), _lib.ptr(g_rot), _lib.ptr(g_cov), accumulate,
                                       C.cast(C.pointer(fuse_c), C.c_void_p) if fuse_c is not None else None)
-            alloc = _lib.TorchAllocator(device)
-            try:
-                rc = L.gp_raster_backward(C.byref(st), C.byref(inp), C.byref(out), C.byref(saved), _lib.ptr(gc), _lib.ptr(gd),
-                                          C.byref(grads), alloc.cb, None, _lib.stream_ptr(device))
-                if alloc.error is not None:
-                    raise alloc.error
+            with _lib.TorchAllocator(device) as alloc:
+                rc = L.gp_raster_backward(st, inp, out, saved, gc, gd, grads, alloc.cb, None, _lib.stream_ptr(device))
                 _lib.check(rc, "gp_raster_backward")
-            finally:
-                alloc.release()
         if fuse is not None:         # the kernel rewrote the two parameters through raw pointers: keep their version counters honest
             _bump_version(leaf_sh)
             _bump_version(leaf_rest)
@@ -277,8 +263,7 @@ class GaussianRasterizer(nn.Module):
             vm = self.raster_settings.viewmatrix.detach().to(torch.float32).contiguous()
             present = torch.empty(p.shape[0], dtype=torch.uint8, device=p.device)
             with _lib.on_device(p.device):
-                rc = _lib.lib().gp_raster_mark_visible(C.c_int64(p.shape[0]), _lib.ptr(p), _lib.ptr(vm), _lib.ptr(present),
-                                                      _lib.stream_ptr(p.device))
+                rc = _lib.lib().gp_raster_mark_visible(p.shape[0], p, vm, present, _lib.stream_ptr(p.device))
                 _lib.check(rc, "gp_raster_mark_visible")
         return present.bool()
 
@@ -319,26 +304,19 @@ def raster_forward_debug(raster_settings, means3D, opacities, shs=None, colors_p
         tidx = torch.empty(H, W, device=device, dtype=torch.int32)
         out = _lib.RasterOutputsC(_lib.ptr(color), _lib.ptr(radii), _lib.ptr(depth), _lib.ptr(tidx))
         saved = _lib.RasterSavedC()
-        alloc = _lib.TorchAllocator(device)
-        try:
-            _lib.check(L.gp_raster_forward(C.byref(st), C.byref(inp), C.byref(out), C.byref(saved), alloc.cb, None,
-                                           _lib.stream_ptr(device)), "gp_raster_forward")
-        except BaseException:
-            alloc.release()
-            raise
-        R = int(saved.num_rendered)
-        T = ((W + 15) // 16) * ((H + 15) // 16)
-        point_list = torch.empty(max(R, 1), dtype=torch.int32, device=device)
-        ranges = torch.empty(T, 2, dtype=torch.int32, device=device)
-        _lib.check(L.gp_raster_debug_binning(C.byref(st), C.byref(saved), _lib.ptr(point_list), _lib.ptr(ranges),
-                                             _lib.stream_ptr(device)), "gp_raster_debug_binning")
-        torch.cuda.synchronize(device)
-        geom = alloc.first(_lib.GP_BUF_GEOM)
-        rec = geom[:48 * N].view(torch.float32).view(N, 12).clone() if (geom is not None and N > 0) else None
-        img = alloc.first(_lib.GP_BUF_IMAGE)
-        al = lambda v: (v + 255) // 256 * 256                     # ImageLayout of gp_capi_raster.hip: 256-byte aligned arrays
-        nc_off = al(al(8 * (T + 8)) + 4 * H * W)               # ranges[T] + the instance counter's 16 slots, final_T[P], n_contrib[P]
-        n_contrib = img[nc_off:nc_off + 4 * H * W].view(torch.int32).view(H, W).clone() if img is not None else None
-        alloc.release()
+        with _lib.TorchAllocator(device) as alloc:
+            _lib.check(L.gp_raster_forward(st, inp, out, saved, alloc.cb, None, _lib.stream_ptr(device)), "gp_raster_forward")
+            R = int(saved.num_rendered)
+            T = ((W + 15) // 16) * ((H + 15) // 16)
+            point_list = torch.empty(max(R, 1), dtype=torch.int32, device=device)
+            ranges = torch.empty(T, 2, dtype=torch.int32, device=device)
+            _lib.check(L.gp_raster_debug_binning(st, saved, point_list, ranges, _lib.stream_ptr(device)), "gp_raster_debug_binning")
+            torch.cuda.synchronize(device)
+            geom = alloc.first(_lib.GP_BUF_GEOM)
+            rec = geom[:48 * N].view(torch.float32).view(N, 12).clone() if (geom is not None and N > 0) else None
+            img = alloc.first(_lib.GP_BUF_IMAGE)
+            al = lambda v: (v + 255) // 256 * 256                     # ImageLayout of gp_capi_raster.hip: 256-byte aligned arrays
+            nc_off = al(al(8 * (T + 8)) + 4 * H * W)               # ranges[T] + the instance counter's 16 slots, final_T[P], n_contrib[P]
+            n_contrib = img[nc_off:nc_off + 4 * H * W].view(torch.int32).view(H, W).clone() if img is not None else None
     return dict(color=color, radii=radii, depth=depth, tidx=tidx, R=R, point_list=point_list[:R], ranges=ranges, rec=rec,
                 n_contrib=n_contrib)

@@ -23,7 +23,6 @@ their own checkers for the two kernels it reaches (the Adam step, furthest-point
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from types import SimpleNamespace
 
@@ -87,8 +86,8 @@ def furthest_point_sampling(xyz: torch.Tensor, m: int) -> torch.Tensor:
         idx = torch.empty(m, dtype=torch.int32, device=x.device)
         tmp = torch.empty(n, dtype=torch.float32, device=x.device)
         with _lib.on_device(x.device):
-            _lib.check(_lib.lib().gp_furthest_point_sampling(C.c_int64(n), _lib.ptr(x), C.c_int64(m), _lib.ptr(idx), _lib.ptr(tmp),
-                                                             _lib.stream_ptr(x.device)), "gp_furthest_point_sampling")
+            _lib.check(_lib.lib().gp_furthest_point_sampling(n, x, m, idx, tmp, _lib.stream_ptr(x.device)),
+                       "gp_furthest_point_sampling")
         return idx.to(torch.int64)
     if host_fps is None:
         raise RuntimeError("furthest_point_sampling: HIP kernel only (no CPU fallback)")

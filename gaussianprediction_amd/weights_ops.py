@@ -11,20 +11,15 @@ tinycudann / frnn are absent from the reference tree: parity unpinned (oracle/we
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 
 import torch
 from torch import nn
 
 from . import _lib
+from ._lib import HashGridConfigC  # noqa: F401  (gp_hashgrid_config; callers name it weights_ops.HashGridConfigC)
 
 MLP_FLOATS = 64 * 64 + 64 * 64 + 16 * 64
-
-
-class HashGridConfigC(C.Structure):   # == gp_hashgrid_config
-    _fields_ = [("n_levels", C.c_int32), ("n_features_per_level", C.c_int32), ("log2_hashmap_size", C.c_int32),
-                ("base_resolution", C.c_int32), ("per_level_scale", C.c_float)]
 
 
 def _need_cuda(t, what):
@@ -58,8 +53,7 @@ class _HashGridEncode(torch.autograd.Function):
         n = x.shape[0]
         out = torch.empty(n, cfg.n_levels * 4, device=x.device)
         with _lib.on_device(x.device):
-            _lib.check(_lib.lib().gp_hashgrid_forward(C.byref(cfg), C.c_int64(n), _lib.ptr(x), _lib.ptr(perm), _lib.ptr(t),
-                                                      _lib.ptr(out), _lib.stream_ptr(x.device)), "gp_hashgrid_forward")
+            _lib.check(_lib.lib().gp_hashgrid_forward(cfg, n, x, perm, t, out, _lib.stream_ptr(x.device)), "gp_hashgrid_forward")
         ctx.save_for_backward(x)
         ctx.perm = perm
         ctx.cfg, ctx.table_shape = cfg, table.shape
@@ -71,8 +65,7 @@ class _HashGridEncode(torch.autograd.Function):
         g = g.to(torch.float32).contiguous()
         dtable = torch.zeros(ctx.table_shape, device=x.device)
         with _lib.on_device(x.device):
-            _lib.check(_lib.lib().gp_hashgrid_backward(C.byref(ctx.cfg), C.c_int64(x.shape[0]), _lib.ptr(x), _lib.ptr(ctx.perm),
-                                                       _lib.ptr(g), _lib.ptr(dtable), _lib.stream_ptr(x.device)),
+            _lib.check(_lib.lib().gp_hashgrid_backward(ctx.cfg, x.shape[0], x, ctx.perm, g, dtable, _lib.stream_ptr(x.device)),
                        "gp_hashgrid_backward")
         return None, dtable, None, None
 
@@ -90,8 +83,7 @@ class _WeightsModelFused(torch.autograd.Function):
         out = torch.empty(n, n_out, device=x.device)
         feat = torch.empty(n, 64, device=x.device) if need else None
         with _lib.on_device(x.device):
-            _lib.check(_lib.lib().gp_weights_forward(C.byref(cfg), C.c_int64(n), _lib.ptr(x), _lib.ptr(perm), _lib.ptr(p),
-                                                     C.c_int32(n_out), _lib.ptr(out), _lib.ptr(feat), _lib.stream_ptr(x.device)),
+            _lib.check(_lib.lib().gp_weights_forward(cfg, n, x, perm, p, n_out, out, feat, _lib.stream_ptr(x.device)),
                        "gp_weights_forward")
         if need:
             ctx.save_for_backward(x, p, feat)
@@ -107,16 +99,10 @@ class _WeightsModelFused(torch.autograd.Function):
         if sink is not None and grad_sink.take_stale(sink):
             sink.zero_()
         dparams = sink if sink is not None else torch.zeros_like(p)
-        alloc = _lib.TorchAllocator(x.device)
-        with _lib.on_device(x.device):
-            rc = _lib.lib().gp_weights_backward(C.byref(ctx.cfg), C.c_int64(x.shape[0]), _lib.ptr(x), _lib.ptr(ctx.perm), _lib.ptr(p),
-                                                C.c_int32(ctx.n_out), _lib.ptr(feat), _lib.ptr(g), _lib.ptr(dparams), alloc.cb, None,
+        with _lib.TorchAllocator(x.device) as alloc:
+            rc = _lib.lib().gp_weights_backward(ctx.cfg, x.shape[0], x, ctx.perm, p, ctx.n_out, feat, g, dparams, alloc.cb, None,
                                                 _lib.stream_ptr(x.device))
-        err = alloc.error
-        alloc.release()
-        if err is not None:
-            raise err
-        _lib.check(rc, "gp_weights_backward")
+            _lib.check(rc, "gp_weights_backward")
         if sink is not None:
             grad_sink.notify(ctx.leaf)
             return None, None, None, None, None
@@ -142,7 +128,7 @@ class WeightsModel(nn.Module):
             per_level_scale = math.exp(math.log(2048 / base_resolution) / (n_levels - 1))   # [REF :372]
         self.n_output_dims = n_output_dims
         self.cfg = HashGridConfigC(n_levels, n_features_per_level, log2_hashmap_size, base_resolution, per_level_scale)
-        entries = int(_lib.lib().gp_hashgrid_table_entries(C.byref(self.cfg)))
+        entries = int(_lib.lib().gp_hashgrid_table_entries(self.cfg))
         if entries < 0:
             raise RuntimeError(_lib.lib().gp_last_error().decode(errors='replace'))
         self.table_entries = entries
@@ -188,10 +174,8 @@ def knn_keypoints(xyz, kp_xyz, nearest_num, feat=None, kp_feat=None, feature_amp
     if order is not None and (order.dtype != torch.int32 or order.shape[0] != n or not order.is_contiguous() or order.device != x.device):
         raise RuntimeError("knn: order must be a contiguous int32 permutation of the points, on their device")
     with _lib.on_device(x.device):
-        rc = _lib.lib().gp_knn_keypoints(C.c_int64(n), _lib.ptr(x), _lib.ptr(f), C.c_int32(f.shape[1] if hybrid else 0),
-                                         C.c_float(feature_amplify), C.c_int64(K), _lib.ptr(k), _lib.ptr(kf),
-                                         C.c_int32(nearest_num), _lib.ptr(order), _lib.ptr(idx), _lib.ptr(d2), _lib.ptr(idx16),
-                                         _lib.stream_ptr(x.device))
+        rc = _lib.lib().gp_knn_keypoints(n, x, f, f.shape[1] if hybrid else 0, feature_amplify, K, k, kf, nearest_num, order, idx,
+                                         d2, idx16, _lib.stream_ptr(x.device))
         _lib.check(rc, "gp_knn_keypoints")
     if idx16 is not None:
         idx._gp_idx16 = ((idx._version, idx.data_ptr(), tuple(idx.shape)), idx16)      # (deform_ops.packed_idx16 finds it here)
@@ -205,6 +189,6 @@ def dist_cuda2(points):
     x = points.detach().to(torch.float32).contiguous()
     out = torch.empty(x.shape[0], device=x.device)
     with _lib.on_device(x.device):
-        _lib.check(_lib.lib().gp_knn3_mean_dist2(C.c_int64(x.shape[0]), _lib.ptr(x), _lib.ptr(out), _lib.stream_ptr(x.device)),
+        _lib.check(_lib.lib().gp_knn3_mean_dist2(x.shape[0], x, out, _lib.stream_ptr(x.device)),
                    "gp_knn3_mean_dist2")
     return out

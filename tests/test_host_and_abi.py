@@ -128,7 +128,8 @@ _STRUCTS = {"gp_raster_settings": "RasterSettingsC", "gp_raster_inputs": "Raster
             "gp_raster_saved": "RasterSavedC", "gp_raster_grads": "RasterGradsC", "gp_adam_fuse": "AdamFuseC",
             "gp_mlp_params": "MlpParamsC", "gp_mlp16_params": "Mlp16ParamsC", "gp_mlp_grads": "MlpGradsC",
             "gp_mlp_input": "MlpInputC", "gp_blend_args": "BlendArgsC", "gp_profile_entry": "ProfileEntryC",
-            "gp_step_plan": "StepPlanC", "gp_step_view": "StepViewC", "gp_step_update": "StepUpdateC"}
+            "gp_step_plan": "StepPlanC", "gp_step_view": "StepViewC", "gp_step_update": "StepUpdateC",
+            "gp_hashgrid_config": "HashGridConfigC"}
 
 
 def _header_layout(tmp_path):
@@ -203,3 +204,154 @@ def test_integration_stub_matches_header_and_binding(tmp_path):
             assert {k.arg for k in node.keywords} <= {n for n, *_ in ns[node.func.id]._fields_}, node.func.id
             seen.add(node.func.id)
     assert seen == {"RasterSettingsC", "RasterInputsC", "RasterOutputsC", "RasterSavedC", "RasterGradsC"}
+
+
+# ---- one signature per entry point, two statements of it: include/gp_hip.h and _lib.PROTOTYPES ----
+_SCALARS = {"int": C.c_int32, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint32_t": C.c_uint32, "float": C.c_float,
+            "size_t": C.c_size_t, "gp_stream_t": _lib.Ptr, "gp_alloc_fn": _lib.Ptr}
+_POINTEES = {"float", "double", "void", "int", "int8_t", "int16_t", "int32_t", "int64_t", "uint8_t", "uint16_t", "uint32_t", "uint64_t"}
+
+
+def _header_prototypes():
+    """{name: (return type, [parameter type])} of include/gp_hip.h, types as text without `const` and the parameter name."""
+    hdr = open(os.path.join(ROOT, "include", "gp_hip.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
+    hdr = re.sub(r"^\s*#.*$", "", hdr, flags=re.M)
+    hdr = re.sub(r"typedef struct \w*\s*\{.*?\}\s*\w+\s*;", "", hdr, flags=re.S)
+    hdr = re.sub(r"enum\s*\{.*?\}\s*;", "", hdr, flags=re.S)
+    protos = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][\w\s\*]*?)\b(gp_[a-z_0-9]+)\s*\(([^;{]*?)\)\s*;", hdr):
+        assert name not in protos, name
+        params = " ".join(params.split())
+        plist = [] if params in ("", "void") else [re.sub(r"\s*\w+$", "", p.strip()) for p in params.split(",")]
+        protos[name] = (" ".join(ret.split()), [" ".join(t.replace("const", " ").replace("*", " * ").split()) for t in plist])
+    return protos
+
+
+def _class_of(ctype):
+    """The argtypes class section 1 of the binding's rules gives a parameter of C type `ctype`."""
+    if "*" not in ctype:
+        return _SCALARS[ctype]
+    base = ctype.split("*")[0].strip()
+    if base in _STRUCTS:
+        assert ctype == base + " *", ctype
+        return C.POINTER(getattr(_lib, _STRUCTS[base]))
+    assert base in _POINTEES, ctype
+    return _lib.Ptr
+
+
+def test_prototype_table_equals_the_header():
+    protos = _header_prototypes()
+    assert set(protos) == set(_lib.PROTOTYPES) == set(_lib.EXPORTS), set(protos) ^ set(_lib.PROTOTYPES)
+    assert len(protos) == len(_lib.EXPORTS) == 61
+    for name, (ret, params) in protos.items():
+        restype, argtypes = _lib.PROTOTYPES[name]
+        assert restype is {"int": C.c_int32, "int64_t": C.c_int64, "const char*": C.c_char_p}[ret], (name, ret, restype)
+        assert len(argtypes) == len(params), (name, params, argtypes)
+        for k, (ctype, cls) in enumerate(zip(params, argtypes)):
+            assert cls is _class_of(ctype), (name, k, ctype, cls)
+    assert _lib.PROTOTYPES["gp_raster_forward"][1][0]._type_ is _lib.RasterSettingsC           # (POINTER(X) is cached: `is` compares X)
+    from gaussianprediction_amd import weights_ops
+    assert weights_ops.HashGridConfigC is _lib.HashGridConfigC
+
+
+def test_prototype_table_is_applied_to_the_library():
+    l = _lib.lib()
+    for name, (restype, argtypes) in _lib.PROTOTYPES.items():
+        fn = getattr(l, name)
+        assert fn.restype is restype, name
+        assert list(fn.argtypes) == list(argtypes), name
+
+
+def test_argument_width_survives_without_a_wrapper():
+    l = _lib.lib()
+    rc = l.gp_raster_mark_visible(1 << 32, None, None, None, None)     # (cut to 32 bits this is n == 0: the early return, rc 0)
+    assert rc != 0 and b"n out of range" in l.gp_last_error()
+    assert l.gp_mlp_scratch_bytes(250) == 8192 + 4 * 250 * 256 * 4
+
+
+def test_wrong_argument_kinds_are_refused_before_the_library_runs():
+    l = _lib.lib()
+    with pytest.raises(C.ArgumentError):
+        l.gp_debug_option(0.5, 0)                                      # float for int32_t
+    with pytest.raises(C.ArgumentError):
+        l.gp_mlp_scratch_bytes(C.c_int32(250))                         # c_int32 for int64_t
+    st = _lib.RasterSettingsC(0, 0, 1.0, 1.0, 1.0, 3, 16, 0, 0, None, None, None, None)
+    inp = _lib.RasterInputsC(0, None, None, None, None, None, None, None, None)
+    out, saved = _lib.RasterOutputsC(None, None, None, None), _lib.RasterSavedC()
+    with pytest.raises(C.ArgumentError):
+        l.gp_raster_forward(inp, C.byref(inp), C.byref(out), C.byref(saved), None, None, None)    # gp_raster_inputs for the settings
+    with pytest.raises(C.ArgumentError):
+        l.gp_raster_forward(C.byref(inp), C.byref(inp), C.byref(out), C.byref(saved), None, None, None)
+    assert l.gp_raster_forward(st, inp, out, saved, None, None, None) != 0 and b"image size" in l.gp_last_error()   # instance == byref
+    # the pointer class: a tensor is its data_ptr(); None, wide ints, ctypes arrays, byref, c_void_p and callbacks as c_void_p takes them
+    t = torch.zeros(4)
+    assert _lib.Ptr.from_param(t).value == t.data_ptr()
+    assert _lib.Ptr.from_param(None) is None
+    alloc = _lib.TorchAllocator("cpu")
+    for ok in ((1 << 40) + 8, (C.c_uint64 * 4)(), C.byref(C.c_int(0)), C.c_void_p(16), _lib.ptr(t), alloc.cb):
+        _lib.Ptr.from_param(ok)
+    alloc.release()
+    for bad in (0.5, st):
+        with pytest.raises(TypeError):
+            _lib.Ptr.from_param(bad)
+
+
+def test_every_call_site_passes_as_many_arguments_as_the_prototype_has():
+    """ctypes accepts surplus positional arguments in silence and most call sites only run on a GPU: count them in the source."""
+    import ast
+    import glob
+    files = [os.path.join(ROOT, "bench.py"), os.path.join(ROOT, "__graft_entry__.py")]
+    for d in ("gaussianprediction_amd", "tools", "tests"):
+        files += glob.glob(os.path.join(ROOT, d, "**", "*.py"), recursive=True)
+    examined = 0
+    for path in sorted(files):
+        for node in ast.walk(ast.parse(open(path).read(), path)):
+            if isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr in _lib.PROTOTYPES:
+                assert not node.keywords, (path, node.lineno)
+                if any(isinstance(a, ast.Starred) for a in node.args):
+                    continue
+                examined += 1
+                assert len(node.args) == len(_lib.PROTOTYPES[node.func.attr][1]), (os.path.relpath(path, ROOT), node.lineno, node.func.attr)
+    assert examined >= 100, examined
+
+
+def test_allocator_block_releases_on_every_path_and_prefers_the_callback_error():
+    l = _lib.lib()
+    st = _lib.RasterSettingsC(0, 0, 1.0, 1.0, 1.0, 3, 16, 0, 0, None, None, None, None)       # image size 0: the library refuses
+    inp = _lib.RasterInputsC(0, None, None, None, None, None, None, None, None)
+    out, saved = _lib.RasterOutputsC(None, None, None, None), _lib.RasterSavedC()
+
+    def failing_call(alloc):
+        rc = l.gp_raster_forward(st, inp, out, saved, alloc.cb, None, None)
+        assert rc != 0
+        return rc
+
+    with _lib.TorchAllocator("cpu") as alloc:                          # success: the buffers are reachable inside the block
+        assert alloc.cb(None, _lib.GP_BUF_GEOM, 64) == alloc.first(_lib.GP_BUF_GEOM).data_ptr()
+        assert alloc.first(_lib.GP_BUF_IMAGE) is None
+    assert alloc.bufs is None and alloc.cb is None
+
+    with pytest.raises(KeyError):                                      # allocator error + library error: the allocator's comes out
+        with _lib.TorchAllocator("cpu") as alloc:
+            assert not alloc.cb(None, 99, 64)                          # (no such buffer class: the callback catches a KeyError)
+            assert isinstance(alloc.error, KeyError)
+            _lib.check(failing_call(alloc), "gp_raster_forward")
+    assert alloc.bufs is None
+
+    with pytest.raises(KeyError):                                      # allocator error although the call returned 0
+        with _lib.TorchAllocator("cpu") as alloc:
+            alloc.cb(None, 99, 64)
+            _lib.check(0, "nothing")
+    assert alloc.bufs is None
+
+    with pytest.raises(_lib.GpHipError, match="image size"):           # library error alone
+        with _lib.TorchAllocator("cpu") as alloc:
+            _lib.check(failing_call(alloc), "gp_raster_forward")
+    assert alloc.bufs is None
+
+    with pytest.raises(ZeroDivisionError):                             # an unrelated exception passes through
+        with _lib.TorchAllocator("cpu") as alloc:
+            alloc.cb(None, _lib.GP_BUF_TEMP, 16)
+            1 / 0
+    assert alloc.bufs is None

@@ -2,7 +2,7 @@
 """How many tile-splat instances of the bench workload (configs[2]) can touch NO pixel of their tile at alpha >= 1/255 (sub-block mask 0:
 the 3-sigma rectangle of the published algorithm reaches the tile, the threshold ellipse does not), and how many sub-blocks the others touch.
     python tools/probe/mask_stats.py [--scale 1.0]"""
-import argparse, ctypes as C, json, os, sys
+import argparse, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from types import SimpleNamespace
 import torch
@@ -40,19 +40,18 @@ def main():
             depth = torch.empty(1, H, W, device=dev); tidx = torch.empty(H, W, device=dev, dtype=torch.int32)
             o_c = _lib.RasterOutputsC(_lib.ptr(color), _lib.ptr(radii), _lib.ptr(depth), _lib.ptr(tidx))
             saved = _lib.RasterSavedC()
-            alloc = _lib.TorchAllocator(dev)
-            _lib.check(L.gp_raster_forward(C.byref(st), C.byref(inp), C.byref(o_c), C.byref(saved), alloc.cb, None, _lib.stream_ptr(dev)), "fwd")
-            torch.cuda.synchronize()
-            R = int(saved.num_rendered)
-            b = alloc.first(_lib.GP_BUF_BINNING)
-            off = (R * 4 + 255) // 256 * 256
-            sm = b[off:off + 2 * R].view(torch.int16).to(torch.int32) & 0xFFFF
+            with _lib.TorchAllocator(dev) as alloc:
+                _lib.check(L.gp_raster_forward(st, inp, o_c, saved, alloc.cb, None, _lib.stream_ptr(dev)), "fwd")
+                torch.cuda.synchronize()
+                R = int(saved.num_rendered)
+                b = alloc.first(_lib.GP_BUF_BINNING)
+                off = (R * 4 + 255) // 256 * 256
+                sm = b[off:off + 2 * R].view(torch.int16).to(torch.int32) & 0xFFFF
             # a tile whose pixels all saturated early leaves the tail of its list unstaged (mask never written): count only staged ones
             pop = torch.zeros_like(sm)
             for k in range(16):
                 pop += (sm >> k) & 1
             hist = torch.bincount(pop, minlength=17).tolist()
-            alloc.release()
         out[f"cam{ci}"] = {"R": R, "R_per_gaussian": round(R / N, 3), "empty_mask_frac": round(hist[0] / R, 4),
                           "mean_subblocks_of_nonempty": round(float((pop.float().sum() / max(R - hist[0], 1))), 3), "popcount_hist": hist}
     print(json.dumps(out))
