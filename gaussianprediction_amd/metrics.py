@@ -8,7 +8,10 @@ that never read a number back per view.
 
 MS-SSIM follows the published five-scale form as pytorch_msssim computes it; that package is absent here, so parity with it is
 unpinned (the definition is restated in include/gp_hip.h and checked against a float64 torch restatement in the tests).
-LPIPS is not provided: it needs pretrained network weights this package does not ship.  HIP only: CPU tensors raise."""
+LPIPS (the AlexNet and VGG16 backbones) lives in lpips.py and is re-exported here: `LPIPS`, `lpips`, `find_lpips_weights`; the caller
+supplies the pretrained weight files, this package ships none and never fetches any.  The evaluation loops take it as an option
+(`evaluate_views(lpips=[...])`, `evaluate_dirs(lpips_weights=...)`) and then report the reference's LPIPS-vgg / LPIPS-alex keys
+[REF metrics.py:144-145, 157-162].  HIP only: CPU tensors raise."""
 from __future__ import annotations
 
 import json
@@ -18,6 +21,7 @@ from types import SimpleNamespace
 import torch
 
 from . import _lib
+from .lpips import LPIPS, find_lpips_weights, lpips  # noqa: F401  (re-exported)
 
 NAMES = ("L1", "MSE", "PSNR", "PSNR_CH", "SSIM", "MS_SSIM", "D_SSIM", "reserved")
 L1, MSE, PSNR, PSNR_CH, SSIM, MS_SSIM, D_SSIM = range(7)
@@ -115,23 +119,33 @@ def _times(cameras, times, dev):
 
 
 def evaluate_views(model, cameras, gts, pipe, bg, iteration, *, quantize8=True, ms_ssim=True, speculative=True, clamp=False,
-                   times=None, renderer=None):
+                   times=None, renderer=None, lpips=None):
     """Render every camera and score it against gts[v] ([3,H,W]) without a host read per view: the frames go through
     `SpeculativeRenderer`, each frame's metrics call takes that frame's overflow word as `invalid_flag`, and the [V,8] table is read
     ONCE at the end.  A ring of frames ends in one `flush()`; only if that flush had to re-render frames (their rows are NaN) are
     the ring's rows looked at, and the NaN ones recomputed from the replaced images.  speculative=False renders every frame with
     `render()` in its exact mode (one synchronisation inside each).  Returns {"summary": {"SSIM", "PSNR", "MS-SSIM", "D-SSIM",
     "L1": means over the views, the reference's key names [REF metrics.py:157-162]}, "per_view": the [V,8] float64 device table,
-    "rerendered": frames rendered again}."""
-    table, m, again = _score_views(model, cameras, gts, pipe, bg, iteration, speculative, times, renderer,
-                                   dict(quantize8=quantize8, ms_ssim=ms_ssim, clamp=clamp))
+    "rerendered": frames rendered again}.
+    lpips: a list of `LPIPS` objects.  Each frame's LPIPS call takes the same overflow word and the same quantised render as its
+    metrics call, its rows stay on the device until the one read at the end, and rows redone after an overflow are redone for LPIPS
+    too; the summary gains "LPIPS-vgg" / "LPIPS-alex" and the result "per_view_lpips": {net_type: the [V,8] device table}."""
+    nets = list(lpips or [])
+    table, m, again, ltabs = _score_views(model, cameras, gts, pipe, bg, iteration, speculative, times, renderer,
+                                          dict(quantize8=quantize8, ms_ssim=ms_ssim, clamp=clamp), nets)
     summary = {"SSIM": float(m[SSIM]), "PSNR": float(m[PSNR]), "MS-SSIM": float(m[MS_SSIM]), "D-SSIM": float(m[D_SSIM]), "L1": float(m[L1])}
-    return {"summary": summary, "per_view": table, "rerendered": again}
+    result = {"summary": summary, "per_view": table, "rerendered": again}
+    if nets:
+        host = torch.stack([t[:, 0] for t in ltabs]).cpu()           # (one read for all the nets)
+        for k, net in enumerate(nets):
+            summary[f"LPIPS-{net.net_type}"] = float(host[k].mean())
+        result["per_view_lpips"] = {net.net_type: t for net, t in zip(nets, ltabs)}
+    return result
 
 
-def _score_views(model, cameras, gts, pipe, bg, iteration, speculative, times, renderer, kw):
+def _score_views(model, cameras, gts, pipe, bg, iteration, speculative, times, renderer, kw, nets=()):
     """The loop behind evaluate_views / report_views: (the [V,8] device table, its column means from the ONE host read, frames
-    rendered again)."""
+    rendered again, one [V,8] device table per LPIPS object of `nets`)."""
     from .renderer import SpeculativeRenderer, render
     dev = bg.device
     V = len(cameras)
@@ -139,12 +153,19 @@ def _score_views(model, cameras, gts, pipe, bg, iteration, speculative, times, r
         raise RuntimeError(f"evaluate_views: {V} cameras but {len(gts)} ground-truth images")
     times = _times(cameras, times, dev)
     table = torch.full((V, METRIC_COUNT), float("nan"), dtype=torch.float64, device=dev)
+    ltabs = [torch.full((V, METRIC_COUNT), float("nan"), dtype=torch.float64, device=dev) for _ in nets]
     again = 0
+
+    def score(img, row, flag):
+        image_metrics(img, gts[row], out=table[row:row + 1], invalid_flag=flag, **kw)
+        for net, lt in zip(nets, ltabs):
+            net(img, gts[row], quantize8=kw["quantize8"], out=lt[row:row + 1], invalid_flag=flag)
+
     with torch.no_grad():
         if not speculative:
             for v in range(V):
                 img = render(cameras[v], model, pipe, bg, time=times[v], it=iteration)["render"]
-                image_metrics(img, gts[v], out=table[v:v + 1], **kw)
+                score(img, v, None)
         else:
             sr = renderer if renderer is not None else SpeculativeRenderer(model, pipe, bg)
             sr.flush()          # (a caller's renderer: its ring starts empty, so ring and rows stay in step)
@@ -158,7 +179,7 @@ def _score_views(model, cameras, gts, pipe, bg, iteration, speculative, times, r
                     bad = torch.isnan(table[lo:hi, L1]).cpu()       # (only after an overflow: the rows to do again)
                     for row, img in ring:
                         if bool(bad[row - lo]):
-                            image_metrics(img, gts[row], out=table[row:row + 1], **kw)
+                            score(img, row, None)
                     again += n
                 ring = []
 
@@ -167,17 +188,17 @@ def _score_views(model, cameras, gts, pipe, bg, iteration, speculative, times, r
                     close_ring()
                 img = sr(cameras[v], time=times[v], it=iteration)["render"]
                 st = sr.last_status
-                image_metrics(img, gts[v], out=table[v:v + 1], invalid_flag=None if st is None else st[1:2], **kw)
+                score(img, v, None if st is None else st[1:2])
                 if st is not None:
                     ring.append((v, img))
             close_ring()
-    return table, table.cpu().mean(dim=0), again
+    return table, table.cpu().mean(dim=0), again, ltabs
 
 
 def report_views(model, cameras, gts, pipe, bg, iteration, *, speculative=True, times=None, renderer=None):
     """The `training_report` form [REF train.py:252-282]: both images clamped to [0, 1], no quantisation, no MS-SSIM; returns
     {"L1": mean L1, "PSNR": mean over the views of the per-channel-mean PSNR, "per_view": the table}."""
-    table, m, _ = _score_views(model, cameras, gts, pipe, bg, iteration, speculative, times, renderer,
+    table, m, _, _ = _score_views(model, cameras, gts, pipe, bg, iteration, speculative, times, renderer,
                                dict(quantize8=False, ms_ssim=False, clamp=True))
     return {"L1": float(m[L1]), "PSNR": float(m[PSNR_CH]), "per_view": table}
 
@@ -195,15 +216,25 @@ def _load_rgb(path, device):
     return (t.to(torch.float32) / 255.0)[None].contiguous().to(device)
 
 
-def evaluate_dirs(path, device="cuda", write=True):
+def _lpips_from(weights, device):
+    """evaluate_dirs' `lpips_weights`: a directory holding the four weight files, or a dict {"vgg": w, "alex": w} with w a
+    directory, a (backbone, lin) pair or {"backbone": ..., "lin": ...} -> [LPIPS vgg, LPIPS alex] (the nets the dict names)."""
+    from . import lpips as _lp
+    if isinstance(weights, dict):
+        return [_lp.cached(net, device, weights[net]) for net in ("vgg", "alex") if net in weights]
+    return [_lp.cached(net, device, os.fspath(weights)) for net in ("vgg", "alex")]
+
+
+def evaluate_dirs(path, device="cuda", write=True, lpips_weights=None):
     """The directory form of the reference's metrics.py [REF metrics.py:113-178]: for every `<path>/<method>/` holding `renders/`
     and `gt/`, score the sorted image pairs (files whose name contains "depth" are skipped), write `<method>/deltas/%05d.jpg` and
     -- as the reference does -- `<path>/results.json` and `<path>/per_view.json` of the last method.  Keys: SSIM, PSNR, MS-SSIM,
-    D-SSIM.  The reference's two LPIPS keys (LPIPS-vgg, LPIPS-alex) are MISSING: they need pretrained VGG / AlexNet weights this
-    package does not ship.  The images were saved as 8 bits already, so nothing is quantised again.  One table read per method.
+    D-SSIM; with `lpips_weights` (a directory holding the weight files find_lpips_weights names, or a dict {"vgg": ..., "alex": ...})
+    the reference's six in its order: SSIM, PSNR, LPIPS-vgg, LPIPS-alex, MS-SSIM, D-SSIM.  The images were saved as 8 bits already, so nothing is quantised again.  One table read per method.
     Returns {method: {"summary": ..., "per_view": ...}} with the dictionaries that were written."""
     from PIL import Image
     device = torch.device(device)
+    nets = _lpips_from(lpips_weights, device) if lpips_weights is not None else []
     result = {}
     for method in sorted(os.listdir(path)):
         mdir = os.path.join(path, method)
@@ -215,18 +246,23 @@ def evaluate_dirs(path, device="cuda", write=True):
         if len(rnames) != len(gnames) or not rnames:
             raise RuntimeError(f"evaluate_dirs: {rdir} holds {len(rnames)} images, {gdir} holds {len(gnames)}")
         table = torch.empty(len(rnames), METRIC_COUNT, dtype=torch.float64, device=device)
+        ltabs = [torch.empty(len(rnames), METRIC_COUNT, dtype=torch.float64, device=device) for _ in nets]
         if write:
             os.makedirs(os.path.join(mdir, "deltas"), exist_ok=True)
         pending = []
         for i, (rn, gn) in enumerate(zip(rnames, gnames)):
-            r = image_metrics(_load_rgb(os.path.join(rdir, rn), device), _load_rgb(os.path.join(gdir, gn), device),
-                              out=table[i:i + 1], deltas=write)
+            render, gt = _load_rgb(os.path.join(rdir, rn), device), _load_rgb(os.path.join(gdir, gn), device)
+            r = image_metrics(render, gt, out=table[i:i + 1], deltas=write)
+            for net, lt in zip(nets, ltabs):
+                net(render, gt, out=lt[i:i + 1])
             if write:
                 pending.append(r.deltas)
-        h = table.cpu()
+        h = table.cpu() if not nets else torch.cat([table] + [lt[:, :1] for lt in ltabs], dim=1).cpu()      # (one read either way)
         for i, d in enumerate(pending):
             Image.fromarray(d[0].cpu().numpy()).save(os.path.join(mdir, "deltas", "{0:05d}.jpg".format(i)))
-        cols = {"SSIM": SSIM, "PSNR": PSNR, "MS-SSIM": MS_SSIM, "D-SSIM": D_SSIM}
+        cols = {"SSIM": SSIM, "PSNR": PSNR}
+        cols.update({f"LPIPS-{net.net_type}": METRIC_COUNT + k for k, net in enumerate(nets)})
+        cols.update({"MS-SSIM": MS_SSIM, "D-SSIM": D_SSIM})
         summary = {k: float(h[:, c].mean()) for k, c in cols.items()}
         per_view = {k: {n: float(h[i, c]) for i, n in enumerate(rnames)} for k, c in cols.items()}
         result[method] = {"summary": summary, "per_view": per_view}

@@ -11,6 +11,10 @@ profiles/metrics_probe.txt.
                                                    `rocprofv3 --kernel-trace --stats -- python tools/metrics_probe.py --kernels-only` run)
     python tools/metrics_probe.py --trace-summary DIR/s_kernel_trace.csv   (no GPU: that run's trace per launch shape -- a pyramid
                                                    level is a grid size -- appended to profiles/metrics_probe.txt)
+    python tools/metrics_probe.py --lpips         (only the LPIPS section: both nets at both sizes, B = 1, with the seeded weights
+                                                   of tests/lpips_ref.py -- the call, the library's brackets per kernel, lpips_conv's
+                                                   TF/s against the measured f32 MFMA peak, every convolution against
+                                                   torch.nn.functional.conv2d on the same device.  Writes profiles/lpips_probe.txt)
 """
 import os
 import sys
@@ -143,6 +147,89 @@ def eval_loop(lines):
         lines.append(f"  render + torch composition + .item() per view       {n / (time.perf_counter() - t0):8.1f} views/s")
 
 
+def lpips_section():
+    import lpips_ref as LR
+    from gaussianprediction_amd import lpips as LP, peaks
+    import torch.nn.functional as F
+    lines = []
+    peak = peaks.measure(str(DEV), gib=0.25, reps=5)["mfma_f32_TFLOPs"]
+    lines.append(f"LPIPS (gp_lpips) on {torch.cuda.get_device_name(DEV)}, B = 1, seeded weights; hipEvent-timed, median of 20 after 3 warm-ups (ms)")
+    lines.append(f"measured f32 MFMA peak (peaks.measure): {peak:.1f} TF/s")
+    st = _lib.stream_ptr(DEV)
+    for H, W in SIZES:
+        a, b = pair(1, H, W)
+        for net in ("vgg", "alex"):
+            w = LR.seeded_weights(net)
+            m = LP.LPIPS(net, w["backbone"], w["lin"], device=DEV)
+            t_hip = timed(lambda: m(a, b))
+            wd = {"backbone": {k: v.to(DEV) for k, v in w["backbone"].items()}, "lin": {k: v.to(DEV) for k, v in w["lin"].items()}}
+            with torch.no_grad():
+                try:
+                    t_t = timed(lambda: LR.lpips_terms(a, b, net, wd, torch.float32), reps=20, warm=3)
+                    d = float((m(a, b).table[0, 0] - LR.lpips_terms(a, b, net, wd, torch.float32)[0, 0].double()).abs())
+                    torch_txt = f"{t_t:9.3f} ms ({t_t / t_hip:5.2f}x of hip)   |hip - torch32| {d:.1e}"
+                except Exception as e:      # noqa: BLE001  (no convolution library on this device: say so)
+                    torch_txt = f"not measured ({type(e).__name__}: {str(e)[:80]})"
+            _lib.profile_enable(2)
+            _lib.profile_collect()
+            for _ in range(5):
+                m(a, b)
+            torch.cuda.synchronize()
+            prof = _lib.profile_collect()
+            _lib.profile_enable(0)
+            # the convolutions' operations, from the library's table: 2 M K Cout each, M the output pixels of both images
+            flop, h, wd_, taps, layers = 0.0, H, W, 0, []
+            for e in LP.network_table(net):
+                if taps == 5:
+                    break
+                if e.kind in (LP.CONV, LP.POOL):
+                    hi, wi = h, wd_
+                    h, wd_ = (h + 2 * e.pad - e.k) // e.stride + 1, (wd_ + 2 * e.pad - e.k) // e.stride + 1
+                    if e.kind == LP.CONV:
+                        f = 2.0 * 2 * h * wd_ * e.k * e.k * e.cin * e.cout
+                        flop += f
+                        layers.append((e, hi, wi, f))
+                taps += e.tap
+            conv_ms = prof["lpips_conv"][1] / 5
+            lines.append("")
+            lines.append(f"{net} {H} x {W}: gp_lpips {t_hip:8.3f} ms   torch float32 composition (F.conv2d / F.max_pool2d, same device) {torch_txt}")
+            lines.append("  per call (ms, launches): " + "  ".join(f"{n} {prof[n][1] / 5:.3f} ({prof[n][0] // 5})" for n in
+                         ("lpips_prepare", "lpips_conv", "lpips_pool", "lpips_dist", "lpips_finalize") if n in prof))
+            lines.append(f"  lpips_conv: {flop / 1e12:.3f} TFLOP per pair in {conv_ms:.3f} ms = {flop / conv_ms / 1e9:.1f} TF/s = "
+                         f"{100 * flop / conv_ms / 1e9 / peak:.0f} % of the measured f32 MFMA peak")
+            lines.append(f"  {'conv':>4s} {'Cin':>4s} {'Cout':>4s} {'k':>2s} {'in H x W':>12s} {'GFLOP':>8s} {'hip ms':>8s} {'TF/s':>6s} {'torch ms':>9s} {'TF/s':>6s}")
+            for e, hi, wi, f in layers:
+                x = torch.randn(2, e.cin, hi, wi, device=DEV)
+                xn = x.permute(0, 2, 3, 1).contiguous()
+                wt, bt = w["backbone"][[k for k in w["backbone"] if k.endswith(".weight")][e.conv]].to(DEV), torch.zeros(e.cout, device=DEV)
+                ho, wo = (hi + 2 * e.pad - e.k) // e.stride + 1, (wi + 2 * e.pad - e.k) // e.stride + 1
+                y, pk = torch.empty(2, ho, wo, e.cout, device=DEV), torch.empty(wt.numel(), device=DEV)
+                run = lambda: _lib.check(LP.lib().gp_lpips_conv2d_relu(xn, wt, bt, pk, y, 2, hi, wi, e.cin, e.cout, e.k, e.stride, e.pad, st), "conv")   # noqa: E731
+                run()
+                _lib.profile_enable(2)
+                _lib.profile_collect()
+                for _ in range(5):
+                    run()
+                torch.cuda.synchronize()
+                t_l = _lib.profile_collect()["lpips_conv"][1] / 5
+                _lib.profile_enable(0)
+                try:
+                    with torch.no_grad():
+                        t_tl = timed(lambda: F.relu(F.conv2d(x, wt, bt, stride=e.stride, padding=e.pad)), reps=10, warm=2)
+                    tt = f"{t_tl:9.3f} {f / t_tl / 1e9:6.1f}"
+                except Exception as ex:      # noqa: BLE001
+                    tt = f"not measured ({type(ex).__name__})"
+                lines.append(f"  {e.conv:4d} {e.cin:4d} {e.cout:4d} {e.k:2d} {f'{hi} x {wi}':>12s} {f / 1e9:8.2f} {t_l:8.3f} {f / t_l / 1e9:6.1f} {tt}")
+                del x, xn, y
+            del m
+            torch.cuda.empty_cache()
+    text = "\n".join(lines) + "\n"
+    print(text, end="")
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "lpips_probe.txt"), "w") as f:
+        f.write(text)
+
+
 def trace_summary(path):
     """Mean duration per (kernel, grid) of a rocprofv3 kernel trace, in order of first appearance."""
     import csv
@@ -168,6 +255,9 @@ def main():
     if "--trace-summary" in sys.argv:
         trace_summary(sys.argv[sys.argv.index("--trace-summary") + 1])
         return
+    if "--lpips" in sys.argv:
+        lpips_section()
+        return
     if "--kernels-only" in sys.argv:
         for H, W in SIZES:
             for B in (1, 8):
@@ -186,6 +276,8 @@ def main():
     os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
     with open(os.path.join(ROOT, "profiles", "metrics_probe.txt"), "w") as f:
         f.write(text)
+    if "--no-lpips" not in sys.argv:
+        lpips_section()
 
 
 if __name__ == "__main__":
