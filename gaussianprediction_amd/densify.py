@@ -8,6 +8,8 @@
     keypoint growth in the second stage                     -> GaussianModel.densification_motion_postfix / densify_kpts
 
 The operations themselves are methods of the model (training.py), as in the reference; this module is the loop-side driver.
+track_view_device / densification_step_device run the first four lines on the device instead (densify_ops, include/gp_densify.h):
+the same rows, moments and optimizer outcome; not the default.
 """
 from __future__ import annotations
 
@@ -18,6 +20,15 @@ def track_view(model, viewspace_point_tensor, visibility_filter, radii):
     """[REF train.py:166-167]"""
     model.max_radii2D[visibility_filter] = torch.max(model.max_radii2D[visibility_filter], radii[visibility_filter].to(torch.float32))
     model.add_densification_stats(viewspace_point_tensor, visibility_filter)
+
+
+def track_view_device(model, pkg):
+    """track_view(model, pkg["viewspace_points"], pkg["visibility_filter"], pkg["radii"]) as ONE launch over the N rows
+    (gp_densify_stats) with no host wait: the visibility bytes the projection wrote, the int32 radii and the screen-space gradient
+    go to the kernel as they are [REF train.py:166-167]."""
+    from . import densify_ops
+    densify_ops.stats(pkg["visibility_filter"], pkg["radii"], pkg["viewspace_points"].grad, model.max_radii2D,
+                      model.xyz_gradient_accum, model.denom, model.xyz_gradient_accum_max)
 
 
 def held_groups(model, iteration, opt, white_background=False):
@@ -52,6 +63,24 @@ def densification_step(model, iteration, opt, scene_extent, max_gaussian_size=20
     if due:
         n_pruned = model.prune(opt.densify_grad_threshold, 0.005, scene_extent, size_threshold)
     return n_clone, n_src, n_pruned
+
+
+def densification_step_device(model, iteration, opt, scene_extent, max_gaussian_size=200_000, white_background=False, generator=None):
+    """densification_step() on the device path: when the surgery is due, densify / reset_opacity / prune are one
+    GaussianModel.densify_prune_device call (one plan, one apply, one host read, one optimizer rebuild); an iteration that is only
+    an opacity reset goes to the in-place reset_opacity().  Same arguments, same return triple.  A seeded run draws its split
+    positions differently from densification_step() (see densify_prune_device)."""
+    due = iteration > opt.densify_from_iter and iteration % opt.densification_interval == 0
+    size_threshold = 20 if iteration > opt.opacity_reset_interval else None
+    do_reset = iteration % opt.opacity_reset_interval == 0 or (white_background and iteration == opt.densify_from_iter)
+    if not due:
+        if do_reset:
+            model.reset_opacity()
+        return None, None, None
+    do_densify = model.get_xyz.shape[0] < max_gaussian_size
+    n_clone, n_src, n_pruned = model.densify_prune_device(opt.densify_grad_threshold, 0.005, scene_extent, size_threshold, do_densify,
+                                                          do_reset, generator=generator)
+    return (n_clone, n_src, n_pruned) if do_densify else (None, None, n_pruned)
 
 
 def keypoint_growth_step(model, iteration, opt, args, visibility_filter=None, radii=None, viewspace_point_tensor=None):

@@ -386,19 +386,25 @@ class TrainingMixin:
         `optimizer.step()` has not): some non-stale gradient buffer is not all zero.  This package's own harness updates first
         and operates afterwards (everything is zero -- Adam zeroes in the same launch -- or marked stale); the reference's loop
         runs densify / prune / reset_opacity BETWEEN backward and optimizer.step() [REF train.py:164-197].  One host read."""
+        flag = self._unconsumed_gradient_flag(params)
+        return False if flag is None else bool(flag)
+
+    def _unconsumed_gradient_flag(self, params=None):
+        """_unconsumed_gradient() before its host read: None (nothing live) or a 0-dim bool tensor on the gradients' device."""
         if self.bucket is None:
-            return False
+            return None
         from . import grad_sink
         live = [self.bucket.segment(p) for p in (self.bucket.params if params is None else params)
                 if p.grad is not None and not grad_sink.is_stale(p.grad)]
         live = [seg for seg in live if seg.numel() > 0]
         if not live:
-            return False
-        return bool(torch.stack([seg.abs().max() for seg in live]).max() > 0)
+            return None
+        return torch.stack([seg.abs().max() for seg in live]).max() > 0
 
-    def _rebuild_optimizer(self, carried):
+    def _rebuild_optimizer(self, carried, pending=None):
         """New bucket + optimizer over the model's CURRENT Parameters.  `carried` maps id(new per-Gaussian Parameter) to its
-        (exp_avg, exp_avg_sq); every other parameter keeps its moments; step count and learning rates are preserved.
+        (exp_avg, exp_avg_sq); every other parameter keeps its moments; step count and learning rates are preserved.  `pending`:
+        what _unconsumed_gradient() says, from a caller that has read it already (None: read here).
 
         Loops in the reference's order [REF train.py:164-197: backward -> densify / prune -> optimizer.step()] arrive here with an
         unconsumed gradient in the old bucket.  torch.optim.Adam would then update the parameters that SURVIVED the surgery (MLP,
@@ -408,7 +414,8 @@ class TrainingMixin:
         old = self.optimizer
         if old is None:
             return
-        pending = self._unconsumed_gradient()
+        if pending is None:
+            pending = self._unconsumed_gradient()
         old_bucket = self.bucket
         old_off = {id(p): off for p, off in zip(old_bucket.params, old_bucket.offsets)}
         old_mom = self.adam_moments()
@@ -598,6 +605,62 @@ class TrainingMixin:
         if self.optimizer is not None:           # in place, on every rank its own slice (no collective, no temporaries)
             self.optimizer.zero_moments(self._opacity)
         self.assert_ranks_agree("reset_opacity")
+
+    def densify_prune_device(self, max_grad, min_opacity, extent, max_screen_size, do_densify, do_reset, generator=None):
+        """What densify() (when `do_densify`), reset_opacity() (when `do_reset`) and prune() leave, in that order, from one plan,
+        one apply and one optimizer rebuild (densify_ops; include/gp_densify.h).  Returns (n_cloned, n_split_sources, n_pruned).
+
+        Rows, copied fields, Adam moments, statistics, step count, `lag`, learning rates, `pending_hold` and the handling of an
+        unconsumed gradient are those of the existing sequence.  ONE host read: the status block (the new row count sizes the
+        outputs) together with the unconsumed-gradient flag that _rebuild_optimizer would otherwise read for itself.
+
+        The split draws are torch.randn(2, N, 3) on the device -- a size known without a read -- from `generator`,
+        _surgery_generator() under view parallelism or `deterministic_surgery`, else torch's global stream; copy c of source i is
+        placed with normals[c, i].  This consumes the random stream differently from densify()'s torch.normal(std=stds[sel]): a
+        seeded run splits to different, equally valid positions than on the existing path.  Ranks with the same seed get identical
+        rows (assert_ranks_agree runs inside the rebuild).
+
+        Not provided for a sharded optimizer (`optimizer_shard`: the moments live as 1/world slices)."""
+        if getattr(self, "optimizer_shard", None) is not None:
+            raise NotImplementedError("densify_prune_device: the optimizer is sharded (optimizer_shard) -- its moments live as slices; "
+                                      "use densify() / reset_opacity() / prune() (densify.densification_step)")
+        from . import densify_ops as D
+        self._sync_side_stream()
+        P = {k: v.detach() for k, v in self._per_gaussian().items()}
+        mom = self.adam_moments()
+        mom_in = {k: mom.get(id(p)) for k, p in self._per_gaussian().items()}
+        n, dev = P["xyz"].shape[0], P["xyz"].device
+        if dev.type != "cuda":
+            raise RuntimeError(f"densify_prune_device: the model is on {dev} -- HIP kernels only (no CPU fallback); use densify() / prune()")
+        if not float(max_grad) > 0:
+            raise ValueError(f"densify_prune_device: max_grad must be > 0 (got {max_grad})")
+        normals = None
+        if do_densify:
+            if generator is None:
+                generator = self._surgery_generator()
+            self._surgery_no += 1
+            normals = torch.randn(2, n, 3, generator=generator, device=dev)
+        stats_in = (self.xyz_gradient_accum, self.denom, self.xyz_gradient_accum_max, self.max_radii2D)
+        scratch, status, flags = D.plan(self.xyz_gradient_accum, self.denom, self.max_radii2D, P["scaling"], P["opacity"], max_grad,
+                                        self.percent_dense * extent, min_opacity, max_screen_size, 0.1 * extent,
+                                        do_densify=do_densify, do_reset=do_reset, do_prune=True)
+        flag = self._unconsumed_gradient_flag() if self.optimizer is not None else None
+        words = status if flag is None else torch.cat([status, flag.to(torch.int32).reshape(1)])
+        host = words.tolist()                                   # the one host read
+        n_clone, n_src, n_pruned, rows = host[D.ST_CLONED], host[D.ST_SPLIT], host[D.ST_PRUNED], host[D.ST_ROWS]
+        pending = bool(host[D.STATUS_WORDS]) if flag is not None else False
+        out = {k: torch.empty((rows,) + tuple(v.shape[1:]), device=dev) for k, v in P.items()}
+        mom_out = {k: (None if mom_in[k] is None else (torch.empty_like(out[k]), torch.empty_like(out[k]))) for k in P}
+        stats_out = tuple(torch.empty((rows,) + tuple(t.shape[1:]), device=dev) for t in stats_in)
+        D.apply(n, [(k, P[k], mom_in[k], out[k], mom_out[k]) for k in P], normals, stats_in, stats_out, rows, flags, scratch, status)
+        fresh = {}
+        for name, attr in PER_GAUSSIAN:
+            if name in out:
+                fresh[name] = nn.Parameter(out[name].requires_grad_(True))
+                setattr(self, attr, fresh[name])
+        self.xyz_gradient_accum, self.denom, self.xyz_gradient_accum_max, self.max_radii2D = stats_out
+        self._rebuild_optimizer({id(fresh[k]): mv for k, mv in mom_out.items() if mv is not None}, pending=pending)
+        return n_clone, n_src, n_pruned
 
     # ---- keypoint growth -----------------------------------------------------------------------------------------------
     def new_kpts_init(self):                      # [REF :170-172]
