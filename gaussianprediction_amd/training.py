@@ -748,17 +748,28 @@ class TrainingMixin:
         self.new_kpts_init()
 
     @torch.no_grad()
-    def set_superKeypoints(self, seed=0):
+    def set_superKeypoints(self, seed=0, device_kmeans=None):
         """k-means of [xyz | motion_feature] -> K = max_points keypoints: positions = per-cluster mean of the Gaussian
-        positions, features = the motion-feature part of the cluster centres [REF scene/gaussian_model.py:127-136]."""
+        positions, features = the motion-feature part of the cluster centres [REF scene/gaussian_model.py:127-136].
+        device_kmeans (default: args.kmeans_device, off): the deterministic device k-means (kmeans_ops.kmeans, args.kmeans_iters
+        iterations, stop at args.kmeans_tol) in place of the torch composition."""
         self._sync_side_stream()
         xyz = self.get_xyz.detach()
         feature = torch.cat([xyz, self.motion_feature.detach()], dim=-1)
-        ids, centres = kmeans(feature, int(self.args.max_points), seed=seed)
-        K = centres.shape[0]
-        sums = torch.zeros(K, 3, device=xyz.device).index_add_(0, ids, xyz)
-        cnt = torch.zeros(K, device=xyz.device).index_add_(0, ids, torch.ones(xyz.shape[0], device=xyz.device))
-        means = torch.where(cnt[:, None] > 0, sums / cnt[:, None].clamp_min(1), centres[:, :3])
+        if device_kmeans is None:
+            device_kmeans = getattr(self.args, "kmeans_device", False)
+        if device_kmeans:
+            from . import kmeans_ops
+            res = kmeans_ops.kmeans(feature.contiguous(), int(self.args.max_points), iters=int(getattr(self.args, "kmeans_iters", 20)),
+                                    tol=float(getattr(self.args, "kmeans_tol", 0.0)), seed=seed, aux=xyz.contiguous())
+            centres = res.centres
+            means = torch.where(res.counts[:, None] > 0, res.aux_mean, centres[:, :3])
+        else:
+            ids, centres = kmeans(feature, int(self.args.max_points), seed=seed)
+            K = centres.shape[0]
+            sums = torch.zeros(K, 3, device=xyz.device).index_add_(0, ids, xyz)
+            cnt = torch.zeros(K, device=xyz.device).index_add_(0, ids, torch.ones(xyz.shape[0], device=xyz.device))
+            means = torch.where(cnt[:, None] > 0, sums / cnt[:, None].clamp_min(1), centres[:, :3])
         kf, kp = centres[:, 3:].contiguous(), means.contiguous()
         self._vp_broadcast([kp, kf])             # (index_add_ sums with float atomics on the device: rank 0's result is everyone's)
         self.super_gaussians_feature = nn.Parameter(kf.requires_grad_(True))
