@@ -155,6 +155,9 @@ def _prototypes():
         "gp_raster_backward": (i32, [st, inp, out, saved, P, P, S(RasterGradsC), P, P, P]),
         "gp_raster_mark_visible": (i32, [i64, P, P, P, P]),
         "gp_raster_debug_binning": (i32, [st, saved, P, P, P]),
+        "gp_debug_sort_pairs": (i32, [i32, P, P, i64, i32, P, P, P, P, P, P]),
+        "gp_debug_scan_blocks": (i32, [P, i64, P, P, P]),
+        "gp_debug_bin_lists": (i32, [i32, i64, i32, i32, P, P, i64, P, P, P, P, P]),
         "gp_mlp_scratch_bytes": (i64, [i64]),
         "gp_mlp_packed_floats": (i64, [i32]),
         "gp_mlp_pack": (i32, [mlp, P, P]),

@@ -6,6 +6,7 @@
 #include "loss_adam_kernels.h"     // GpLossPrologue
 #include <stdlib.h>
 #include <atomic>
+#include <vector>
 
 thread_local char gp_err_buf[512] = "";
 static std::atomic<uint32_t> g_key_tag{0};       // numbers the forward calls that check a depth-key promise (never 0)
@@ -104,6 +105,113 @@ struct ImageLayout {
     }
 };
 
+// The binning stage of the forward: from the depth-ordered Gaussians (ids, tile rectangles, tile counts) to the per-tile lists and
+// their ranges.  One statement of the sequence for gp_raster_forward and for gp_debug_bin_lists (the tests run what ships).
+struct GpBinStage {
+    RasterDims d;                   // N, gx and key_tag are read
+    size_t T;
+    const uint32_t* sorted_ids;     // [N] Gaussian ids in depth order
+    const uint2* rects;             // [N] tile rectangles in depth order
+    uint32_t* tt;                   // [N] tiles per Gaussian in depth order (duplicate path: scanned in place)
+    uint32_t* block_sums;           // one word per GP_SCAN_TILE Gaussians (duplicate path)
+    bool counting;                  // gp_bin_supported(N, T): binning by counting, else duplicate + radix sort
+    GpBinPlan bp;
+    uint32_t* binhist;              // bp.hist_elems words (counting path)
+    int64_t capacity;               // gp_raster_settings.binning_capacity
+    uint32_t* status;               // gp_raster_settings.binning_status
+    int2* ranges;                   // [T], zero on entry
+    uint32_t* total;                // GP_TOTAL_SLOTS words, zero on entry
+    uint32_t* order;                // [T] the composite forward's tile order (written by the counting path: order_done)
+};
+// R: the instances binned (capacity mode: the capacity).  BINNING is asked from `alloc` (point_list[R], then room for the composite
+// forward's sub-block masks: this stage writes the first R words only) and handed back in bin / bin_bytes.
+static int gp_binning_stage(const GpBinStage& b, gp_alloc_fn alloc, void* alloc_ctx, hipStream_t s, uint32_t& R, uint32_t*& point_list,
+                            void*& bin_out, size_t& bin_bytes_out, bool& order_done) {
+    const RasterDims& d = b.d;
+    const size_t N = (size_t)d.N, T = b.T;
+    const uint32_t* sorted_ids = b.sorted_ids;
+    const uint2* rects = b.rects;
+    uint32_t* tt = b.tt;
+    const bool counting = b.counting;
+    const GpBinPlan& bp = b.bp;
+    uint32_t* binhist = b.binhist;
+    // tile counts -> instance offsets: scanned inside blocks here, finished by the duplicate kernel (one launch, not three)
+    uint32_t* block_sums = b.block_sums;
+    if (counting) {         // per-(block, tile) instance counts; the blocks' totals go into the R slots
+        GpProfScope _p("bin_count", s);
+        if (gp_bin_count(bp, N, d.gx, T, rects, binhist, b.total, s)) return 1;
+    } else if (gp_scan_blocks_u32(tt, N, block_sums, b.total, s)) return 1;
+    const bool capacity_mode = b.capacity > 0;
+    if (capacity_mode) {    // no host synchronisation: everything below is sized by the caller's capacity
+        if (!b.status) GP_FAIL("binning_capacity needs binning_status (device, 2 words)");
+        if (b.capacity > 0x7FFFFF00ll) GP_FAIL("binning_capacity too large");
+        R = (uint32_t)b.capacity;          // (the status word and the sentinel keys are written by the duplicate launch)
+    } else {
+        uint32_t slots[GP_TOTAL_SLOTS];
+        GP_HIP_CHECK(hipMemcpyAsync(slots, b.total, sizeof(slots), hipMemcpyDeviceToHost, s));
+        GP_HIP_CHECK(hipStreamSynchronize(s));
+        uint64_t Rsum = 0;
+        for (int k = 0; k < GP_TOTAL_SLOTS; ++k) Rsum += slots[k];
+        if (Rsum > 0x7FFFFF00ull) GP_FAIL("too many tile-splat instances (%llu)", (unsigned long long)Rsum);
+        R = (uint32_t)Rsum;
+        if (R > 0x7FFFFF00u) GP_FAIL("too many tile-splat instances (%u)", R);
+        if (b.status && (!counting || R == 0)) {   // exact mode reports R too (a caller sizing its capacity reads it from here; the counting path's scatter writes it)
+            hipLaunchKernelGGL(gp_binning_status_kernel, dim3(1), dim3(1), 0, s, b.total, 0xFFFFFFFFu, b.status, d.key_tag);
+            GP_LAUNCH_CHECK();
+        }
+    }
+
+    if (R > 0 && counting) {
+        const size_t bin_bytes = gp_align_up((size_t)R * 4, 256) + gp_align_up(2 * (size_t)R + 8, 256);
+        void* bin = alloc(alloc_ctx, GP_BUF_BINNING, bin_bytes);
+        if (!bin) GP_FAIL("allocator returned NULL for BINNING");
+        point_list = (uint32_t*)bin;
+        bin_out = bin; bin_bytes_out = bin_bytes;
+        if (gp_bin_scatter(bp, N, d.gx, T, sorted_ids, rects, binhist, point_list, R, b.ranges, b.status, b.order, d.key_tag, s)) return 1;
+        order_done = true;
+    } else if (R > 0) {
+        // capacity mode pads the keys with 0xFFFFFFFF: its low `tbits` bits must sort behind every real tile id
+        const int tbits = tile_bits_for((int)T + (capacity_mode ? 1 : 0));
+        const int passes = (tbits + 7) / 8;
+        const int res = passes & 1;  // buffer pair holding the sorted result
+        // BINNING = point_list[R] (u32) followed by smask[R] (u16: which 4x4 sub-blocks of its tile an instance can touch)
+        const size_t bin_bytes = gp_align_up((size_t)R * 4, 256) + gp_align_up(2 * (size_t)R + 8, 256);
+        void* bin = alloc(alloc_ctx, GP_BUF_BINNING, bin_bytes);
+        if (!bin) GP_FAIL("allocator returned NULL for BINNING");
+        point_list = (uint32_t*)bin;
+        bin_out = bin; bin_bytes_out = bin_bytes;
+        const size_t bh = gp_sort_hist_elems(R), bs = gp_scan_tmp_elems(256 * (((size_t)R + 4095) / 4096));
+        auto carve_bin = [&](GpCarver& c, uint32_t*& bk0, uint32_t*& bk1, uint32_t*& bvo, uint32_t*& bhist, uint32_t*& bscan) {
+            bk0 = c.take<uint32_t>(R); bk1 = c.take<uint32_t>(R); bvo = c.take<uint32_t>(R);
+            bhist = c.take<uint32_t>(bh); bscan = c.take<uint32_t>(bs);
+        };
+        uint32_t *bk0, *bk1, *bvo, *bhist, *bscan;
+        GpCarver bc0(nullptr);
+        carve_bin(bc0, bk0, bk1, bvo, bhist, bscan);
+        void* btmp = alloc(alloc_ctx, GP_BUF_TEMP, bc0.bytes());
+        if (!btmp) GP_FAIL("allocator returned NULL for TEMP (%zu B)", bc0.bytes());
+        GpCarver bc(btmp);
+        carve_bin(bc, bk0, bk1, bvo, bhist, bscan);
+        GpSortBufs tb;
+        tb.k[0] = bk0; tb.k[1] = bk1;
+        tb.v[res] = point_list; tb.v[res ^ 1] = bvo;
+        tb.hist = bhist; tb.scan_tmp = bscan; tb.scan_tmp_elems = bs;
+        { GpProfScope _p("duplicate", s);
+        const unsigned ndup = gp_blocks(N, 256);
+        hipLaunchKernelGGL(gp_duplicate_kernel, dim3(ndup + (capacity_mode ? gp_blocks(R, 4096) : 0u)), dim3(256), 0, s, d, sorted_ids, tt,
+                           (const uint32_t*)block_sums, (const uint32_t*)b.total, rects, tb.k[0], tb.v[0], R, b.status, ndup, d.key_tag);
+        GP_LAUNCH_CHECK(); }
+        int r2;
+        { GpProfScope _p("tile_sort", s); r2 = gp_radix_sort_pairs(tb, R, tbits, s); }
+        if (r2 < 0) return 1;
+        if (r2 != res) GP_FAIL("internal: sort parity mismatch");
+        { GpProfScope _p("tile_ranges", s);
+        hipLaunchKernelGGL(gp_tile_ranges_kernel, dim3(gp_blocks(R, 256)), dim3(256), 0, s, tb.k[r2], R, (uint32_t)T, b.ranges);
+        GP_LAUNCH_CHECK(); }
+    }
+    return 0;
+}
+
 extern "C" int gp_raster_forward(const gp_raster_settings* st, const gp_raster_inputs* in, gp_raster_outputs* out,
                                  gp_raster_saved* saved, gp_alloc_fn alloc, void* alloc_ctx, gp_stream_t stream_) {
     hipStream_t s = (hipStream_t)stream_;
@@ -194,80 +302,12 @@ extern "C" int gp_raster_forward(const gp_raster_settings* st, const gp_raster_i
         { GpProfScope _p("depth_sort", s); r1 = (dsort3 && key_bits == 32) ? gp_depth_sort3(sb, N, dshist, s, &ep) : gp_radix_sort_pairs(sb, N, key_bits, s, true, &ep); }
         if (r1 < 0) return 1;
         const uint32_t* sorted_ids = sb.v[r1];
-        // tile counts -> instance offsets: scanned inside blocks here, finished by the duplicate kernel (one launch, not three)
-        uint32_t* block_sums = scan_tmp;
-        if (counting) {         // per-(block, tile) instance counts; the blocks' totals go into the R slots
-            GpProfScope _p("bin_count", s);
-            if (gp_bin_count(bp, N, d.gx, T, rects, binhist, il.total, s)) return 1;
-        } else if (gp_scan_blocks_u32(tt, N, block_sums, il.total, s)) return 1;
-        const bool capacity_mode = st->binning_capacity > 0;
-        if (capacity_mode) {    // no host synchronisation: everything below is sized by the caller's capacity
-            if (!st->binning_status) GP_FAIL("binning_capacity needs binning_status (device, 2 words)");
-            if (st->binning_capacity > 0x7FFFFF00ll) GP_FAIL("binning_capacity too large");
-            R = (uint32_t)st->binning_capacity;          // (the status word and the sentinel keys are written by the duplicate launch)
-        } else {
-            uint32_t slots[GP_TOTAL_SLOTS];
-            GP_HIP_CHECK(hipMemcpyAsync(slots, il.total, sizeof(slots), hipMemcpyDeviceToHost, s));
-            GP_HIP_CHECK(hipStreamSynchronize(s));
-            uint64_t Rsum = 0;
-            for (int k = 0; k < GP_TOTAL_SLOTS; ++k) Rsum += slots[k];
-            if (Rsum > 0x7FFFFF00ull) GP_FAIL("too many tile-splat instances (%llu)", (unsigned long long)Rsum);
-            R = (uint32_t)Rsum;
-            if (R > 0x7FFFFF00u) GP_FAIL("too many tile-splat instances (%u)", R);
-            if (st->binning_status && (!counting || R == 0)) {   // exact mode reports R too (a caller sizing its capacity reads it from here; the counting path's scatter writes it)
-                hipLaunchKernelGGL(gp_binning_status_kernel, dim3(1), dim3(1), 0, s, il.total, 0xFFFFFFFFu, st->binning_status, d.key_tag);
-                GP_LAUNCH_CHECK();
-            }
-        }
-
-        if (R > 0 && counting) {
-            const size_t bin_bytes = gp_align_up((size_t)R * 4, 256) + gp_align_up(2 * (size_t)R + 8, 256);
-            void* bin = alloc(alloc_ctx, GP_BUF_BINNING, bin_bytes);
-            if (!bin) GP_FAIL("allocator returned NULL for BINNING");
-            point_list = (uint32_t*)bin;
-            saved->binning = bin; saved->binning_bytes = bin_bytes;
-            if (gp_bin_scatter(bp, N, d.gx, T, sorted_ids, rects, binhist, point_list, R, il.ranges, st->binning_status, il.order, d.key_tag, s)) return 1;
-            order_done = true;
-        } else if (R > 0) {
-            // capacity mode pads the keys with 0xFFFFFFFF: its low `tbits` bits must sort behind every real tile id
-            const int tbits = tile_bits_for((int)T + (capacity_mode ? 1 : 0));
-            const int passes = (tbits + 7) / 8;
-            const int res = passes & 1;  // buffer pair holding the sorted result
-            // BINNING = point_list[R] (u32) followed by smask[R] (u16: which 4x4 sub-blocks of its tile an instance can touch)
-            const size_t bin_bytes = gp_align_up((size_t)R * 4, 256) + gp_align_up(2 * (size_t)R + 8, 256);
-            void* bin = alloc(alloc_ctx, GP_BUF_BINNING, bin_bytes);
-            if (!bin) GP_FAIL("allocator returned NULL for BINNING");
-            point_list = (uint32_t*)bin;
-            saved->binning = bin; saved->binning_bytes = bin_bytes;
-            const size_t bh = gp_sort_hist_elems(R), bs = gp_scan_tmp_elems(256 * (((size_t)R + 4095) / 4096));
-            auto carve_bin = [&](GpCarver& c, uint32_t*& bk0, uint32_t*& bk1, uint32_t*& bvo, uint32_t*& bhist, uint32_t*& bscan) {
-                bk0 = c.take<uint32_t>(R); bk1 = c.take<uint32_t>(R); bvo = c.take<uint32_t>(R);
-                bhist = c.take<uint32_t>(bh); bscan = c.take<uint32_t>(bs);
-            };
-            uint32_t *bk0, *bk1, *bvo, *bhist, *bscan;
-            GpCarver bc0(nullptr);
-            carve_bin(bc0, bk0, bk1, bvo, bhist, bscan);
-            void* btmp = alloc(alloc_ctx, GP_BUF_TEMP, bc0.bytes());
-            if (!btmp) GP_FAIL("allocator returned NULL for TEMP (%zu B)", bc0.bytes());
-            GpCarver bc(btmp);
-            carve_bin(bc, bk0, bk1, bvo, bhist, bscan);
-            GpSortBufs tb;
-            tb.k[0] = bk0; tb.k[1] = bk1;
-            tb.v[res] = point_list; tb.v[res ^ 1] = bvo;
-            tb.hist = bhist; tb.scan_tmp = bscan; tb.scan_tmp_elems = bs;
-            { GpProfScope _p("duplicate", s);
-            const unsigned ndup = gp_blocks(N, 256);
-            hipLaunchKernelGGL(gp_duplicate_kernel, dim3(ndup + (capacity_mode ? gp_blocks(R, 4096) : 0u)), dim3(256), 0, s, d, sorted_ids, tt,
-                               (const uint32_t*)block_sums, (const uint32_t*)il.total, rects, tb.k[0], tb.v[0], R, st->binning_status, ndup, d.key_tag);
-            GP_LAUNCH_CHECK(); }
-            int r2;
-            { GpProfScope _p("tile_sort", s); r2 = gp_radix_sort_pairs(tb, R, tbits, s); }
-            if (r2 < 0) return 1;
-            if (r2 != res) GP_FAIL("internal: sort parity mismatch");
-            { GpProfScope _p("tile_ranges", s);
-        hipLaunchKernelGGL(gp_tile_ranges_kernel, dim3(gp_blocks(R, 256)), dim3(256), 0, s, tb.k[r2], R, (uint32_t)T, il.ranges);
-            GP_LAUNCH_CHECK(); }
-        }
+        GpBinStage bs;
+        bs.d = d; bs.T = T; bs.sorted_ids = sorted_ids; bs.rects = rects; bs.tt = tt; bs.block_sums = scan_tmp;
+        bs.counting = counting; bs.bp = bp; bs.binhist = binhist;
+        bs.capacity = st->binning_capacity; bs.status = st->binning_status;
+        bs.ranges = il.ranges; bs.total = il.total; bs.order = il.order;
+        if (gp_binning_stage(bs, alloc, alloc_ctx, s, R, point_list, saved->binning, saved->binning_bytes, order_done)) return 1;
     }
     if (N == 0 && st->binning_status)      // nothing to bin: {R, overflow} = {0, 0} (a stale overflow word would make Adam skip the step)
         GP_HIP_CHECK(hipMemsetAsync(st->binning_status, 0, 2 * sizeof(uint32_t), s));
@@ -447,5 +487,136 @@ extern "C" int gp_raster_debug_binning(const gp_raster_settings* st, const gp_ra
         if (!point_list) GP_FAIL("null point_list");
         GP_HIP_CHECK(hipMemcpyAsync(point_list, saved->binning, (size_t)saved->num_rendered * 4, hipMemcpyDeviceToDevice, s));
     }
+    return 0;
+}
+
+// ---- diagnostic entries over the index primitives (tests/test_gpu_sort_scan.py, tests/test_gpu_binning_direct.py) ------------------
+// Scratch of one call: device blocks from hipMalloc, freed when the call returns (hipFree waits for the device).
+struct GpDebugScratch {
+    std::vector<void*> blocks;
+    uint32_t* point_list = nullptr;         // gp_debug_bin_lists: the caller's list stands in for the BINNING block
+    ~GpDebugScratch() { for (void* p : blocks) (void)hipFree(p); }
+    void* get(size_t bytes) {
+        void* p = nullptr;
+        if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) return nullptr;
+        blocks.push_back(p);
+        return p;
+    }
+    static void* alloc(void* ctx, int which, size_t bytes) {
+        GpDebugScratch* self = (GpDebugScratch*)ctx;
+        return which == GP_BUF_BINNING ? (void*)self->point_list : self->get(bytes);
+    }
+};
+
+extern "C" int gp_debug_sort_pairs(int algo, const uint32_t* keys, const uint32_t* vals, int64_t n, int nbits, const uint32_t* by_value,
+                                   uint32_t* keys_out, uint32_t* vals_out, uint32_t* sorted_out, uint32_t* count_out, gp_stream_t stream_) {
+    hipStream_t s = (hipStream_t)stream_;
+    if (algo != 0 && algo != 1) GP_FAIL("gp_debug_sort_pairs: algo %d (0 = radix, 1 = three counting passes)", algo);
+    if (n < 0 || n > 0x7FFFFFF0LL) GP_FAIL("gp_debug_sort_pairs: n out of range");
+    if (nbits < 1 || nbits > 32) GP_FAIL("gp_debug_sort_pairs: nbits %d out of range (1 .. 32)", nbits);
+    if (by_value && (vals || !sorted_out || !count_out)) GP_FAIL("gp_debug_sort_pairs: by_value needs iota values (vals == NULL), sorted_out and count_out");
+    if (algo == 1 && (nbits != 32 || vals || n > 512LL * 8192LL))
+        GP_FAIL("gp_debug_sort_pairs: the counting sort takes 32 key bits, iota values and n <= %lld", 512LL * 8192LL);
+    if (n == 0) return 0;
+    if (!keys || !keys_out || !vals_out) GP_FAIL("gp_debug_sort_pairs: null argument");
+    const size_t N = (size_t)n;
+    const size_t hist_elems = gp_sort_hist_elems(N), scan_elems = gp_scan_tmp_elems(256 * ((N + 4095) / 4096));
+    const size_t ds_elems = algo == 1 ? gp_dsort_hist_elems(N) : 0;
+    GpSortBufs sb;
+    uint32_t* dshist;
+    auto carve = [&](GpCarver& c) {
+        for (int k = 0; k < 2; ++k) { sb.k[k] = c.take<uint32_t>(N); sb.v[k] = c.take<uint32_t>(N); }
+        sb.hist = c.take<uint32_t>(hist_elems); sb.scan_tmp = c.take<uint32_t>(scan_elems);
+        dshist = c.take<uint32_t>(ds_elems);
+    };
+    GpCarver c0(nullptr);
+    carve(c0);
+    GpDebugScratch scratch;
+    void* tmp = scratch.get(c0.bytes());
+    if (!tmp) GP_FAIL("gp_debug_sort_pairs: hipMalloc of %zu B failed", c0.bytes());
+    GpCarver c(tmp);
+    carve(c);
+    sb.scan_tmp_elems = scan_elems;
+    GP_HIP_CHECK(hipMemcpyAsync(sb.k[0], keys, N * 4, hipMemcpyDeviceToDevice, s));
+    if (vals) GP_HIP_CHECK(hipMemcpyAsync(sb.v[0], vals, N * 4, hipMemcpyDeviceToDevice, s));
+    const GpSortEpilogue ep = {(const uint2*)by_value, (uint2*)sorted_out, count_out};
+    const int r = algo == 1 ? gp_depth_sort3(sb, N, dshist, s, by_value ? &ep : nullptr)
+                            : gp_radix_sort_pairs(sb, N, nbits, s, vals == nullptr, by_value ? &ep : nullptr);
+    if (r < 0) return 1;
+    GP_HIP_CHECK(hipMemcpyAsync(keys_out, sb.k[r], N * 4, hipMemcpyDeviceToDevice, s));
+    GP_HIP_CHECK(hipMemcpyAsync(vals_out, sb.v[r], N * 4, hipMemcpyDeviceToDevice, s));
+    GP_HIP_CHECK(hipStreamSynchronize(s));
+    return 0;
+}
+
+extern "C" int gp_debug_scan_blocks(uint32_t* data, int64_t n, uint32_t* block_sums, uint32_t* total_slots, gp_stream_t stream_) {
+    hipStream_t s = (hipStream_t)stream_;
+    if (n < 0 || n > 0x7FFFFFF0LL) GP_FAIL("gp_debug_scan_blocks: n out of range");
+    if (!total_slots) GP_FAIL("gp_debug_scan_blocks: null argument");
+    GP_HIP_CHECK(hipMemsetAsync(total_slots, 0, GP_TOTAL_SLOTS * sizeof(uint32_t), s));
+    if (n > 0) {
+        if (!data || !block_sums) GP_FAIL("gp_debug_scan_blocks: null argument");
+        if (gp_scan_blocks_u32(data, (size_t)n, block_sums, total_slots, s)) return 1;
+    }
+    GP_HIP_CHECK(hipStreamSynchronize(s));
+    return 0;
+}
+
+extern "C" int gp_debug_bin_lists(int path, int64_t n, int gx, int gy, const uint32_t* sorted_ids, const uint32_t* rect_sorted, int64_t capacity,
+                                  uint32_t* point_list, int32_t* ranges, uint32_t* status, uint32_t* r_out, gp_stream_t stream_) {
+    hipStream_t s = (hipStream_t)stream_;
+    if (path != 0 && path != 1) GP_FAIL("gp_debug_bin_lists: path %d (0 = counting, 1 = duplicate + radix sort)", path);
+    if (n < 0 || n > 0x7FFFFFF0LL) GP_FAIL("gp_debug_bin_lists: n out of range");
+    if (gx < 1 || gy < 1 || gx > 0xFFFF || gy > 0xFFFF || (int64_t)gx * gy > (1LL << 24)) GP_FAIL("gp_debug_bin_lists: bad tile grid %d x %d", gx, gy);
+    if (capacity < 0 || capacity > 0x7FFFFF00LL) GP_FAIL("gp_debug_bin_lists: capacity out of range");
+    if (!ranges || !status || !r_out) GP_FAIL("gp_debug_bin_lists: null argument");
+    const size_t N = (size_t)n, T = (size_t)gx * gy;
+    if (path == 0 && !gp_bin_supported(N, T)) GP_FAIL("gp_debug_bin_lists: binning by counting does not take n = %lld, %zu tiles", (long long)n, T);
+    *r_out = 0;
+    GP_HIP_CHECK(hipMemsetAsync(ranges, 0, T * sizeof(int2), s));
+    if (N == 0) {
+        GP_HIP_CHECK(hipMemsetAsync(status, 0, 2 * sizeof(uint32_t), s));
+        GP_HIP_CHECK(hipStreamSynchronize(s));
+        return 0;
+    }
+    if (!sorted_ids || !rect_sorted) GP_FAIL("gp_debug_bin_lists: null argument");
+    GpBinStage bs;
+    memset(&bs.d, 0, sizeof(bs.d));
+    bs.d.N = (int)n; bs.d.gx = gx; bs.d.gy = gy;
+    bs.T = T; bs.sorted_ids = sorted_ids; bs.rects = (const uint2*)rect_sorted;
+    bs.counting = path == 0;
+    bs.bp = GpBinPlan{0, 0, 0};
+    if (bs.counting) bs.bp = gp_bin_plan(N, T);
+    bs.capacity = capacity; bs.status = status; bs.ranges = (int2*)ranges;
+    const size_t n_sums = (N + GP_SCAN_TILE - 1) / GP_SCAN_TILE + 64;
+    auto carve = [&](GpCarver& c) {
+        bs.tt = c.take<uint32_t>(N + 1); bs.block_sums = c.take<uint32_t>(n_sums); bs.binhist = c.take<uint32_t>(bs.bp.hist_elems);
+        bs.total = c.take<uint32_t>(GP_TOTAL_SLOTS); bs.order = c.take<uint32_t>(T);
+    };
+    GpCarver c0(nullptr);
+    carve(c0);
+    GpDebugScratch scratch;
+    scratch.point_list = point_list;
+    void* tmp = scratch.get(c0.bytes());
+    if (!tmp) GP_FAIL("gp_debug_bin_lists: hipMalloc of %zu B failed", c0.bytes());
+    GpCarver c(tmp);
+    carve(c);
+    GP_HIP_CHECK(hipMemsetAsync(bs.total, 0, GP_TOTAL_SLOTS * sizeof(uint32_t), s));
+    if (!bs.counting) {     // tiles per Gaussian (in the forward: the depth sort's epilogue)
+        std::vector<uint32_t> h(2 * N);
+        GP_HIP_CHECK(hipMemcpyAsync(h.data(), rect_sorted, N * sizeof(uint2), hipMemcpyDeviceToHost, s));
+        GP_HIP_CHECK(hipStreamSynchronize(s));
+        for (size_t i = 0; i < N; ++i) h[i] = (h[2 * i + 1] & 0xFFFFu) * (h[2 * i + 1] >> 16);
+        GP_HIP_CHECK(hipMemcpyAsync(bs.tt, h.data(), N * 4, hipMemcpyHostToDevice, s));
+        GP_HIP_CHECK(hipStreamSynchronize(s));
+    }
+    uint32_t R = 0;
+    uint32_t* pl = nullptr;
+    void* bin = nullptr;
+    size_t bin_bytes = 0;
+    bool order_done = false;
+    if (gp_binning_stage(bs, GpDebugScratch::alloc, &scratch, s, R, pl, bin, bin_bytes, order_done)) return 1;
+    GP_HIP_CHECK(hipStreamSynchronize(s));
+    *r_out = R;
     return 0;
 }

@@ -177,6 +177,30 @@ int gp_raster_mark_visible(int64_t n, const float* means3D, const float* viewmat
 int gp_raster_debug_binning(const gp_raster_settings* st, const gp_raster_saved* saved, uint32_t* point_list,
                             int32_t* ranges, gp_stream_t stream);
 
+/* Diagnostic entries over the index primitives of the binning stage (tests only: tests/test_gpu_sort_scan.py,
+ * tests/test_gpu_binning_direct.py).  Inputs and outputs are the caller's device buffers; scratch is allocated inside the call and
+ * freed before it returns; each call waits for `stream`.
+ *
+ * gp_debug_sort_pairs: stable sort of n (key, value) pairs by the low `nbits` key bits (the bits above are carried along, not
+ * compared).  algo 0 = the LSD radix sort; algo 1 = the depth sort in three 11-bit counting passes, called directly (not through
+ * gp_debug_option(8, 2)): nbits == 32, vals == NULL and n <= 512 * 8192, refused otherwise.  vals == NULL: the values are 0 .. n-1.
+ * by_value [n,2] (optional, vals == NULL only) turns the last pass's epilogue on: sorted_out[pos] = by_value[value at pos] ([n,2]) and
+ * count_out[pos] = (.y & 0xFFFF) * (.y >> 16). */
+int gp_debug_sort_pairs(int algo, const uint32_t* keys, const uint32_t* vals, int64_t n, int nbits, const uint32_t* by_value,
+                        uint32_t* keys_out, uint32_t* vals_out, uint32_t* sorted_out, uint32_t* count_out, gp_stream_t stream);
+/* gp_debug_scan_blocks: exclusive scan of data[0..n) inside blocks of 2048, in place; block_sums[ceil(n / 2048)] = the blocks' totals;
+ * total_slots[16] (zeroed by the call) receive the grand total spread over the slots: only their sum is defined. */
+int gp_debug_scan_blocks(uint32_t* data, int64_t n, uint32_t* block_sums, uint32_t* total_slots, gp_stream_t stream);
+/* gp_debug_bin_lists: the forward's binning stage on its own, from n depth-ordered Gaussians (sorted_ids[n], rect_sorted[n,2] =
+ * (minx | miny << 16, w | h << 16) in tiles of a gx x gy grid) to the per-tile lists.  path 0 = binning by counting, refused where the
+ * forward would not take it (n > 512 * 8192 or more than 8192 tiles); path 1 = scan + duplicate + radix sort by tile + tile ranges.
+ * capacity 0 = exact mode (point_list must hold the instance count R, which the caller knows from the rectangles); capacity > 0 =
+ * the capacity mode of gp_raster_settings.binning_capacity (point_list[capacity]).  The stage writes straight into point_list.
+ * ranges[gx * gy, 2] is zeroed by the call; status[3] = {R, overflow, scratch} as gp_raster_settings.binning_status; *r_out (host) =
+ * the instances binned (R, or the capacity). */
+int gp_debug_bin_lists(int path, int64_t n, int gx, int gy, const uint32_t* sorted_ids, const uint32_t* rect_sorted, int64_t capacity,
+                       uint32_t* point_list, int32_t* ranges, uint32_t* status, uint32_t* r_out, gp_stream_t stream);
+
 /* ---- deformation path ----------------------------------------------------------------------- */
 
 /* Parameters of Deformable_Field(d=4, w=256) [REF scene/deformable_field.py:102-110]: weights are

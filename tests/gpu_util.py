@@ -40,3 +40,24 @@ def hip_forward_debug(st, scene_dev, **kw):
     return raster_forward_debug(rs, scene_dev["means3D"], scene_dev["opacities"], shs=kw.get("shs", scene_dev.get("shs")),
                                 colors_precomp=kw.get("colors_precomp"), scales=kw.get("scales", scene_dev.get("scales")),
                                 rotations=kw.get("rotations", scene_dev.get("rotations")), cov3D_precomp=kw.get("cov3D_precomp"))
+
+
+# ---- u32 device buffers with canaries (test_gpu_sort_scan.py, test_gpu_binning_direct.py) ----
+CANARY_WORDS = 64
+CANARY = 0x5A5A5A5A
+
+
+def u32_to_device(a, device="cuda:0"):
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint32).view(np.int32)).to(device)
+
+
+def canary_buffer(n, device="cuda:0"):
+    """n words + CANARY_WORDS behind them, all of it the canary word: an output position a kernel skips shows up as well."""
+    return torch.full((int(n) + CANARY_WORDS,), CANARY, dtype=torch.int32, device=device)
+
+
+def read_canary_buffer(t, n):
+    """The first n words as u32; asserts that the canaries behind them are intact."""
+    h = t.cpu().numpy().view(np.uint32)
+    assert np.array_equal(h[n:], np.full(CANARY_WORDS, CANARY, dtype=np.uint32)), "canary words behind the output were overwritten"
+    return h[:n]

@@ -64,6 +64,50 @@ def test_abi_validation_errors_are_reported_not_thrown():
         _lib.check(rc, "gp_mlp_forward")
 
 
+def test_debug_index_entries_validate_their_arguments():
+    """gp_debug_sort_pairs / gp_debug_scan_blocks / gp_debug_bin_lists refuse bad arguments before anything touches a device."""
+    l = _lib.lib()
+    err = l.gp_last_error
+
+    def sort(algo, keys, vals, n, nbits, by_value=None, outs=(8, 8, None, None)):
+        return l.gp_debug_sort_pairs(algo, keys, vals, n, nbits, by_value, outs[0], outs[1], outs[2], outs[3], None)
+
+    assert sort(2, 8, None, 4, 32) != 0 and b"algo 2" in err()
+    assert sort(0, 8, None, -1, 32) != 0 and b"n out of range" in err()
+    assert sort(0, 8, None, 1 << 32, 32) != 0 and b"n out of range" in err()          # (cut to 32 bits this is n == 0: rc 0)
+    for nbits in (0, 33):
+        assert sort(0, 8, None, 4, nbits) != 0 and b"nbits" in err()
+    assert sort(0, 8, 8, 4, 32, by_value=8, outs=(8, 8, 8, 8)) != 0 and b"iota values" in err()   # the epilogue indexes by_value with the values
+    assert sort(0, 8, None, 4, 32, by_value=8, outs=(8, 8, None, 8)) != 0 and b"sorted_out" in err()
+    assert sort(1, 8, None, 4, 24) != 0 and b"32 key bits" in err()
+    assert sort(1, 8, 8, 4, 32) != 0 and b"iota values" in err()
+    assert sort(1, 8, None, 512 * 8192 + 1, 32) != 0 and b"n <= 4194304" in err()
+    assert sort(0, None, None, 4, 32) != 0 and b"null argument" in err()
+    assert sort(0, 8, None, 4, 32, outs=(None, 8, None, None)) != 0 and b"null argument" in err()
+    assert sort(0, None, None, 0, 32, outs=(None, None, None, None)) == 0              # nothing to sort
+
+    assert l.gp_debug_scan_blocks(8, -1, 8, 8, None) != 0 and b"n out of range" in err()
+    assert l.gp_debug_scan_blocks(8, 4, 8, None, None) != 0 and b"null argument" in err()
+
+    def bins(path, n, gx, gy, capacity=0, ids=8, rects=8, pl=8, ranges=8, status=8, r_out=None):
+        r = C.c_uint32(77) if r_out is None else r_out
+        return l.gp_debug_bin_lists(path, n, gx, gy, ids, rects, capacity, pl, ranges, status, C.byref(r) if r is not False else None, None)
+
+    assert bins(2, 4, 4, 4) != 0 and b"path 2" in err()
+    assert bins(1, -1, 4, 4) != 0 and b"n out of range" in err()
+    for gx, gy in ((0, 4), (4, 0), (65536, 1), (4097, 4097)):
+        assert bins(1, 4, gx, gy) != 0 and b"bad tile grid" in err()
+    assert bins(1, 4, 4, 4, capacity=-1) != 0 and b"capacity out of range" in err()
+    assert bins(1, 4, 4, 4, capacity=1 << 31) != 0 and b"capacity out of range" in err()
+    assert bins(1, 4, 4, 4, ranges=None) != 0 and b"null argument" in err()
+    assert bins(1, 4, 4, 4, status=None) != 0 and b"null argument" in err()
+    assert bins(1, 4, 4, 4, r_out=False) != 0 and b"null argument" in err()
+    # the counting path is refused where the forward would not take it: no silent switch to the other path
+    assert bins(0, 512 * 8192 + 1, 85, 64) != 0 and b"binning by counting does not take" in err()
+    assert bins(0, 1000, 8193, 1) != 0 and b"binning by counting does not take" in err()
+    assert bins(0, 0, 4, 4) != 0 and b"binning by counting does not take" in err()
+
+
 def test_rasterizer_argument_contract_and_no_cpu_fallback():
     bg = torch.zeros(3)
     rs = gpa.GaussianRasterizationSettings(image_height=32, image_width=32, tanfovx=0.5, tanfovy=0.5, bg=bg,
@@ -243,7 +287,7 @@ def _class_of(ctype):
 def test_prototype_table_equals_the_header():
     protos = _header_prototypes()
     assert set(protos) == set(_lib.PROTOTYPES) == set(_lib.EXPORTS), set(protos) ^ set(_lib.PROTOTYPES)
-    assert len(protos) == len(_lib.EXPORTS) == 61
+    assert len(protos) == len(_lib.EXPORTS) == 64
     for name, (ret, params) in protos.items():
         restype, argtypes = _lib.PROTOTYPES[name]
         assert restype is {"int": C.c_int32, "int64_t": C.c_int64, "const char*": C.c_char_p}[ret], (name, ret, restype)
