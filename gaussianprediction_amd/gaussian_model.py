@@ -286,6 +286,27 @@ class GaussianModel(TrainingMixin, nn.Module):
         teach = self.df_model.forward_fused(self.motion_feature.detach(), self._xyz.detach(), t, xyz_freq, time_freq)
         self.add_desification_stats_motion(delta_xyz - teach[:, 0:3])
 
+    @torch.no_grad()
+    def keypoint_motion(self, t, iteration):
+        """(super_gaussians + delta_xyz [K, 3], delta_q [K, 4]) at time t: the K-row keypoint MLP pass of a stage-2/3 forward alone --
+        what `get_superGaussians + kpts_xyz_motion` and `kpts_rotation_motion` hold after forward(t, iteration), without the blend over
+        all N Gaussians that [REF motion_model/dataset.py:117-135] pays once per training time (motion.keypoint_trajectories)."""
+        if torch.is_tensor(iteration):
+            iteration = iteration.item()
+        if iteration < self.args.jointly_iteration or iteration <= self.second_stage_iter:
+            raise RuntimeError(f"keypoint_motion: iteration {iteration} is before the second stage (second_stage_iter = "
+                               f"{self.second_stage_iter}): there are no keypoints to move yet")
+        a = self.args
+        xyz_freq, time_freq = int(self.xyz_input_dim / 6), self.time_input_dim // 2
+        t_dev = t.to(self._xyz.device, torch.float32).reshape(-1)[:1]
+        noise = getattr(a, "xyz_noise_iteration", 0)
+        kp = self.super_gaussians
+        if noise and ((iteration - self.second_stage_iter) < noise or bool(getattr(self, "reference_rng", False))):
+            kp = kp + torch.randn_like(kp) * 0.1 * (1 - min(1, (iteration - self.second_stage_iter) / noise))
+        delta = self.df_model.forward_fused(self.super_gaussians_feature, kp, t_dev, xyz_freq, time_freq).detach()
+        q = delta[:, 3:7]
+        return self.super_gaussians.detach() + delta[:, 0:3], (torch.nn.functional.normalize(q) if a.norm_rotation else q)
+
     # ---- the hot path [REF scene/gaussian_model.py:231-304] ---------------------------------------
     def stage_transitions(self, iteration):
         """The stage hooks the reference runs inside forward [REF scene/gaussian_model.py:246-250]: at second_stage_iter + 1 the

@@ -1,0 +1,281 @@
+"""No GPU: the float64 restatement (tests/gcn_ref.py) against the values recorded from the reference's own classes
+(tests/golden/gcn.npz, written by tests/golden/make_gcn_vectors.py); include/gp_gcn.h against the binding's table; the refusals that need
+no device; the module surface (state_dict keys, checkpoints, constructor signatures, shims) against tests/golden/gcn_surface.json; the
+dataset's windows and both time-file formats."""
+import ctypes as C
+import importlib
+import inspect
+import json
+import os
+import re
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+import torch
+
+import gcn_ref as R
+from gaussianprediction_amd import _lib, gcn_ops as G, motion
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+SURFACE = json.load(open(os.path.join(HERE, "golden", "gcn_surface.json")))
+GOLD = np.load(os.path.join(HERE, "golden", "gcn.npz"))
+
+
+# ---- the restatement against the recorded reference ---------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", list(R.CONFIGS))
+def test_restatement_matches_the_recorded_reference(name):
+    c, full = R.cfg_of(name), name == R.FULL
+    assert bytes(GOLD[f"{name}/checksum"]).hex() == R.checksum(R.seeded_state(c))
+    got = R.train_pass(c, torch.float64)
+    got["adam_losses"] = R.adam_losses(c, torch.float64)
+    for nr in (False, True):
+        got[f"rollout{int(nr)}_xyz"], got[f"rollout{int(nr)}_rot"] = R.rollout_pass(c, torch.float64, nr)
+    recorded = {k.split("/", 1)[1] for k in GOLD.files if k.startswith(name + "/")} - {"checksum"}
+    assert recorded == set(got), recorded ^ set(got)
+    excluded = 0
+    for k, v in got.items():
+        rec, mine = GOLD[f"{name}/{k}"], (v if k == "adam_losses" else R.summarise(v, full))
+        assert rec.shape == mine.shape and np.isfinite(mine).all(), k
+        if k.startswith("grad.") and R.excluded_bias(k[5:], c):          # true gradient exactly zero: rounding noise on both sides
+            excluded += 1
+            assert np.abs(mine).max() < 1e-10, k
+            continue
+        assert np.abs(rec - mine).max() <= 1e-10 * np.abs(rec).max(), (k, np.abs(rec - mine).max(), np.abs(rec).max())
+    assert excluded == 2 * (1 + 2 * c.num_stage)
+
+
+def test_seeded_batchnorm_state_is_not_trivial():
+    s = R.seeded_state(R.cfg_of("c1"))
+    for suffix, lo, hi in ((".bn1.weight", 0.5, 1.5), (".bn1.bias", -0.3, 0.3), ("running_mean", -0.5, 0.5), ("running_var", 0.5, 2.0)):
+        vs = [v for k, v in s.items() if k.endswith(suffix)]
+        assert vs and all(v.min() >= lo and v.max() <= hi and v.std() > 0.1 * (hi - lo) for v in vs), suffix
+
+
+# ---- one signature per entry point, two statements of it: include/gp_gcn.h and gcn_ops.PROTOTYPES -----------------------------------
+_SCALARS = {"int": C.c_int32, "int32_t": C.c_int32, "int64_t": C.c_int64, "gp_stream_t": _lib.Ptr}
+_POINTEES = {"float", "void"}
+
+
+def _header():
+    return re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "gp_gcn.h")).read(), flags=re.S)
+
+
+def _header_prototypes():
+    hdr = re.sub(r"^\s*#.*$", "", _header(), flags=re.M)
+    protos = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][\w\s\*]*?)\b(gp_[a-z_0-9]+)\s*\(([^;{]*?)\)\s*;", hdr):
+        assert name not in protos, name
+        params = " ".join(params.split())
+        plist = [] if params in ("", "void") else [re.sub(r"\s*\w+$", "", p.strip()) for p in params.split(",")]
+        protos[name] = (" ".join(ret.split()), [" ".join(t.replace("const", " ").replace("*", " * ").split()) for t in plist])
+    return protos
+
+
+def test_prototype_table_equals_the_header():
+    protos = _header_prototypes()
+    assert set(protos) == set(G.PROTOTYPES) and len(protos) == 5, set(protos) ^ set(G.PROTOTYPES)
+    for name, (ret, params) in protos.items():
+        restype, argtypes = G.PROTOTYPES[name]
+        assert restype is {"int": C.c_int32, "int64_t": C.c_int64}[ret], (name, ret)
+        assert len(argtypes) == len(params), (name, len(params), len(argtypes))
+        for k, (ctype, cls) in enumerate(zip(params, argtypes)):
+            if "*" in ctype:
+                assert ctype.split("*")[0].strip() in _POINTEES and cls is _lib.Ptr, (name, k, ctype, cls)
+            else:
+                assert cls is _SCALARS[ctype], (name, k, ctype, cls)
+        assert params == [] or params[-1] == "gp_stream_t" or name == "gp_gcn_scratch_bytes", name
+    assert not set(protos) & set(_lib.PROTOTYPES)
+
+
+def test_symbols_and_constants():
+    defs = {k: int(v) for k, v in re.findall(r"#define (GP_GCN_[A-Z0-9_]+) (\d+)\b", _header())}
+    assert defs["GP_GCN_ABI_VERSION"] == G.GP_GCN_ABI_VERSION == 1
+    l = G.lib()
+    assert l is _lib.lib() and int(l.gp_gcn_abi_version()) == 1
+    for name, (restype, argtypes) in G.PROTOTYPES.items():
+        fn = getattr(l, name)
+        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
+    assert (defs["GP_GCN_MAX_M"], defs["GP_GCN_MAX_F"], defs["GP_GCN_MAX_B"], defs["GP_GCN_MAX_FRAMES"], defs["GP_GCN_MAX_STAGES"]) == \
+        (G.MAX_M, G.MAX_F, G.MAX_B, G.MAX_FRAMES, G.MAX_STAGES) == (4096, 512, 1024, 4096, 16)
+    assert (defs["GP_GCN_ACT_NONE"], defs["GP_GCN_ACT_TANH"], defs["GP_GCN_ACT_RELU"]) == (G.ACT_NONE, G.ACT_TANH, G.ACT_RELU)
+    assert (defs["GP_GCN_BN_OFF"], defs["GP_GCN_BN_EVAL"], defs["GP_GCN_BN_TRAIN"]) == (G.BN_OFF, G.BN_EVAL, G.BN_TRAIN)
+    assert defs["GP_GCN_TABLE_SLOTS"] == G.TABLE_SLOTS == 7
+    hdr = open(os.path.join(ROOT, "include", "gp_gcn.h")).read()
+    for word in ("Association", "Sums over B", "Saved for the backward", "Launches", "6 + 4 num_stage"):
+        assert word in hdr, word                           # the contract text the header owes
+
+
+# ---- refusals: the C entries validate before they look at a pointer or launch --------------------------------------------------------
+def _fwd(B=2, M=8, Fin=4, Fout=4, bn=0, act=0, ptr=None):
+    p = ptr
+    return G.lib().gp_gcn_layer_forward(B, M, Fin, Fout, p, p, 0, p, p, bn, p, p, p, p, act, p, p, p, p, p, p, None)
+
+
+def _bwd(B=2, M=8, Fin=4, Fout=4, bn=0, act=0):
+    return G.lib().gp_gcn_layer_backward(B, M, Fin, Fout, None, None, 0, None, bn, None, None, act, *([None] * 15))
+
+
+def test_c_entries_refuse_without_a_device():
+    err = lambda: G.lib().gp_last_error()
+    for kw, word in ((dict(B=0), b"B = 0"), (dict(B=1025), b"B = 1025"), (dict(M=0), b"M = 0"), (dict(M=4097), b"M = 4097"),
+                     (dict(Fin=0), b"Fin = 0"), (dict(Fin=513), b"Fin = 513"), (dict(Fout=0), b"Fout = 0"), (dict(Fout=513), b"Fout = 513"),
+                     (dict(bn=3), b"bn_mode"), (dict(act=3), b"act"), (dict(B=1, bn=2), b"Expected more than 1 value per channel when training"),
+                     (dict(), b"null")):
+        assert _fwd(**kw) == 1 and word in err(), (kw, err())
+    for kw, word in ((dict(B=1025), b"B = 1025"), (dict(M=4097), b"M = 4097"), (dict(Fin=513), b"Fin = 513"), (dict(Fout=0), b"Fout = 0"),
+                     (dict(bn=1), b"no backward of the eval mode"), (dict(B=1, bn=2), b"Expected more than 1 value"), (dict(), b"null")):
+        assert _bwd(**kw) == 1 and word in err(), (kw, err())
+    q = G.lib().gp_gcn_scratch_bytes
+    assert q(300, 10, 128, 4, 1, 150) > 0 and q(300, 10, 128, 4, 1, 150) < 64 << 20
+    for bad, word in (((0, 10, 128, 4, 1, 150), b"K = 0"), ((1025, 10, 128, 4, 1, 150), b"K = 1025"), ((300, 0, 128, 4, 1, 150), b"T = 0"),
+                      ((300, 10, 513, 4, 1, 150), b"H = 513"), ((300, 10, 128, 17, 1, 150), b"num_stage = 17"),
+                      ((300, 10, 128, 4, 0, 150), b"output_size = 0"), ((300, 10, 128, 4, 1, 0), b"frames = 0"),
+                      ((300, 10, 128, 4, 1, 4097), b"frames = 4097")):
+        assert q(*bad) == -1 and word in err(), bad
+    ro = G.lib().gp_gcn_rollout
+    tail = [None] * 8
+    assert ro(300, 10, 128, 4, 11, 0, None, 0, None, None, 5, 0, *tail[:6]) == 1 and b"exceeds the window" in err()
+    assert ro(300, 10, 128, 4, 1, 0, None, 0, None, None, 5, 0, *tail[:6]) == 1 and b"table" in err()
+    table = (C.c_void_p * (2 * 11 * 7))()
+    assert ro(300, 10, 128, 4, 1, 0, table, len(table) - 1, None, None, 5, 0, *tail[:6]) == 1 and b"table" in err()
+    assert ro(300, 10, 128, 4, 1, 0, table, len(table), None, None, 5, 0, *tail[:6]) == 1 and b"null" in err()
+
+
+def test_python_side_refusals(monkeypatch):
+    x, w = torch.zeros(2, 8, 4), torch.zeros(4, 4)
+    for call in (lambda: G.layer(x, w), lambda: motion.GraphConvolution(4, 4, node_n=8)(x),
+                 lambda: motion.GCN_xyzr(10, 16, 1, 0, 1, 5)(torch.zeros(2, 3, 5, 10), torch.zeros(2, 4, 5, 10)),
+                 lambda: motion.GCN_xyzr(10, 16, 1, 0, 1, 5).eval().rollout(torch.zeros(10, 5, 3), torch.zeros(10, 5, 4), 3, 1, True)):
+        with pytest.raises(RuntimeError, match="no CPU fallback"):
+            call()
+    with pytest.raises(RuntimeError, match="needs eval mode"):
+        motion.GCN_xyzr(10, 16, 1, 0, 1, 5).rollout(torch.zeros(10, 5, 3), torch.zeros(10, 5, 4), 3, 1, True)
+    for cls, args in ((motion.GC_Block, (16, 0.1)), (motion.GCN, (10, 16, 1, 0.5)), (motion.GCN_xyzr, (10, 16, 1, 0.5))):
+        with pytest.raises(NotImplementedError, match="p_dropout"):
+            cls(*args)
+    # what follows runs on tensors that claim to be device tensors (is_cuda patched: no GPU is touched; a launch would fail the test)
+    monkeypatch.setattr(torch.Tensor, "is_cuda", property(lambda self: True))
+    monkeypatch.setattr(G, "lib", lambda: pytest.fail("a launch was reached"))
+    bn = tuple(torch.ones(8 * 4) for _ in range(4))
+    with pytest.raises(ValueError, match="Expected more than 1 value per channel when training"):
+        G.layer(x[:1], w, bn=bn, training=True)
+    with pytest.raises(RuntimeError, match="eval mode"):
+        G.layer(x, w.clone().requires_grad_(True), bn=bn, training=False)
+    for bad, word in ((lambda: G.layer(torch.zeros(2, 4097, 4), w), "M = 4097"), (lambda: G.layer(torch.zeros(2, 8, 513), torch.zeros(513, 4)), "Fin = 513"),
+                      (lambda: G.layer(torch.zeros(1025, 8, 4), w), "B = 1025"), (lambda: G.layer(x, torch.zeros(4, 513)), "Fout = 513"),
+                      (lambda: G.layer(x.double(), w), "torch.float32"), (lambda: G.layer(x, w, att=torch.zeros(7, 7)), "att must be"),
+                      (lambda: G.layer(x, torch.zeros(5, 4)), "does not take Fin"), (lambda: G.layer(x, w, act=7), "act = 7")):
+        with pytest.raises((ValueError, RuntimeError), match=word):
+            bad()
+    xyz, rot = torch.zeros(10, 5, 3), torch.zeros(10, 5, 4)
+    for kw, word in ((dict(frames=0), "frames = 0"), (dict(frames=4097), "frames = 4097"), (dict(output_size=11), "output_size = 11")):
+        a = dict(frames=3, output_size=1)
+        a.update(kw)
+        with pytest.raises(ValueError, match=word):
+            G.rollout(None, 5, 10, 16, 1, a["output_size"], False, xyz, rot, a["frames"], True)
+
+
+def test_keypoint_motion_raises_before_stage_two():
+    from gaussianprediction_amd.gaussian_model import GaussianModel
+    args = SimpleNamespace(beta=0.1, d=4, w=256, feature_dim=32, jointly_iteration=10, second_stage_iteration=40, third_stage_iteration=60)
+    g = GaussianModel(3, args)
+    for it in (1, 10, 40, torch.tensor(40)):
+        with pytest.raises(RuntimeError, match="before the second stage"):
+            g.keypoint_motion(torch.tensor([0.5]), it)
+
+
+# ---- the module surface ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("no_mapping", [False, True])
+def test_state_dict_keys_and_checkpoint(no_mapping, tmp_path):
+    m = motion.GCN_xyzr(10, 16, 1, 0, num_stage=2, node_n=5, no_mapping=no_mapping)
+    keys = SURFACE["state_dict_keys"][str(no_mapping)]
+    assert list(m.state_dict().keys()) == keys
+    assert (f"GCN_r.GCN.gc_out.att" in keys) == no_mapping and ("GCN_r.GCN.gc_out.2.weight" in keys) == (not no_mapping)
+    assert sum(k.endswith("num_batches_tracked") for k in keys) == 2 * 5
+    # a checkpoint with the reference's keys (what train_GCN.py:114 writes) loads strictly, and comes back unchanged
+    c = R.cfg_of("c2" if no_mapping else "c1")
+    state = R.to_torch(R.seeded_state(c), torch.float32)
+    path = os.path.join(tmp_path, "ckpt.pth")
+    torch.save(state, path)
+    m = motion.GCN_xyzr(c.T, c.H, c.out, 0, num_stage=c.num_stage, node_n=c.K, no_mapping=c.no_mapping)
+    assert m.load_state_dict(torch.load(path), strict=True).missing_keys == []
+    back = m.state_dict()
+    assert list(back.keys()) == list(state.keys()) and all(torch.equal(back[k], state[k]) for k in state)
+
+
+def test_signatures_and_reset_parameters():
+    for name, sig in SURFACE["signatures"].items():
+        obj = getattr(motion, name)
+        assert str(inspect.signature(obj.__init__ if inspect.isclass(obj) else obj)) == sig, name
+    torch.manual_seed(0)
+    gc = motion.GraphConvolution(10, 16, node_n=12)
+    stdv = 1.0 / 4.0
+    for p in (gc.weight, gc.att, gc.bias):
+        assert p.abs().max() <= stdv and p.abs().max() > 0.8 * stdv
+    d, i = motion.get_dct_matrix(10)
+    assert np.allclose(d @ i, np.eye(10), atol=1e-12) and np.allclose(d @ d.T, np.eye(10), atol=1e-12)
+
+
+def test_shims_expose_what_train_gcn_imports():
+    assert set(SURFACE["train_GCN_imports"]) == {"motion_model.gcn", "motion_model.dataset"}
+    for mod, names in SURFACE["train_GCN_imports"].items():
+        m = importlib.import_module(mod)
+        assert m.__doc__ and "Not provided" in m.__doc__
+        for n in names:
+            assert getattr(m, n) is getattr(motion, n), (mod, n)
+    assert "Not provided" in importlib.import_module("motion_model").__doc__
+    args = [a for a in inspect.signature(motion.GCN3DDataset.__init__).parameters]
+    assert args == SURFACE["GCN3DDataset_init_args"]
+
+
+# ---- the dataset ----------------------------------------------------------------------------------------------------------------------
+class _FakeModel:
+    """keypoint_motion(t) = (t, 2 t, 3 t) + keypoint index: enough to see which times land in which window."""
+    def __init__(self, K=4):
+        self.super_gaussians = torch.zeros(K, 3)
+        self.calls = []
+
+    def keypoint_motion(self, t, iteration):
+        self.calls.append((float(t), iteration))
+        k = torch.arange(self.super_gaussians.shape[0], dtype=torch.float32)[:, None]
+        return k + float(t) * torch.tensor([1.0, 2.0, 3.0]), k + float(t) * torch.ones(4)
+
+
+def test_dataset_windows_dnerf(tmp_path):
+    times = [i / 20 for i in range(20)]
+    json.dump({"frames": [{"time": t, "file_path": f"./train/r_{i:03d}"} for i, t in enumerate(times)]}, open(tmp_path / "transforms_train.json", "w"))
+    T, O = 5, 2
+    fm = _FakeModel()
+    tr = motion.GCN3DDataset(fm, 6, 123, "out/d-nerf/x", str(tmp_path), max_time=0.8, input_size=T, output_size=O, split="train")
+    assert tr.nodes_num == 4 and tr.train_times == times[:16] and tr.test_times == times[16:]
+    assert [c[1] for c in fm.calls] == [123] * 20
+    assert len(tr) == tr.train_lens == 16 - T - O
+    for i in (0, len(tr) - 1):
+        it = tr[i]
+        assert set(it) == set(SURFACE["item_keys"])
+        assert it["xyz_inputs"].shape == (T, 4, 3) and it["xyz_gt"].shape == (O, 4, 3) and it["rotation_inputs"].shape == (T, 4, 4) and it["rotation_gt"].shape == (O, 4, 4)
+        assert torch.allclose(it["xyz_inputs"][:, 0, 0], torch.tensor(times[i:i + T])) and torch.allclose(it["xyz_gt"][:, 0, 0], torch.tensor(times[i + T:i + T + O]))
+        assert abs(it["time"] - 0.05) < 1e-12
+    te = motion.GCN3DDataset(_FakeModel(), 6, 123, "out/x", str(tmp_path), max_time=0.8, input_size=T, output_size=O, split="test")
+    assert len(te) == 2                                  # test_lens = 4, one window every output_size rows
+    assert torch.allclose(te[0]["xyz_inputs"][:, 0, 0], torch.tensor(times[11:16])) and torch.allclose(te[0]["xyz_gt"][:, 0, 0], torch.tensor(times[16:18]))
+    assert torch.allclose(te[1]["rotation_inputs"][:, 0, 0], torch.tensor(times[13:18])) and torch.allclose(te[1]["rotation_gt"][:, 0, 0], torch.tensor(times[18:20]))
+    with pytest.raises(NotImplementedError, match="val"):
+        motion.GCN3DDataset(_FakeModel(), 6, 123, "out/d-nerf/x", str(tmp_path), input_size=T, output_size=O, split="val")
+
+
+@pytest.mark.parametrize("with_val_ids", [False, True])
+def test_dataset_times_hypernerf(tmp_path, with_val_ids):
+    ids = [f"im{i:03d}" for i in range(41)]
+    json.dump({i: {"warp_id": k, "camera_id": 0} for k, i in enumerate(ids)}, open(tmp_path / "metadata.json", "w"))
+    ds = {"ids": ids, "val_ids": ids[1::2] if with_val_ids else [], "train_ids": ids[0::2]}
+    json.dump(ds, open(tmp_path / "dataset.json", "w"))
+    d = motion.GCN3DDataset(_FakeModel(), 6, 7, "out/hyper/x", str(tmp_path), max_time=0.8, input_size=4, output_size=1, split="train")
+    t = [k / 40 for k in range(41)]
+    if with_val_ids:
+        assert d.train_times == [x for k, x in enumerate(t) if k % 2 == 0 and x < 0.8] and d.test_times == [x for k, x in enumerate(t) if k % 2 == 1 and x >= 0.8]
+    else:
+        assert d.train_times == [x for k, x in enumerate(t) if k % 4 == 0 and x < 0.8] and d.test_times == [x for k, x in enumerate(t) if (k - 2) % 4 == 0 and x >= 0.8]
+    assert len(d) == len(d.train_times) - 5
