@@ -1,0 +1,187 @@
+"""The render-to-disk loops of the reference's eval.py: the test views, a frozen-view sequence over the training times, and the
+interpolated-pose video frames, written as PNG files encoded on the device (png_ops) behind a render loop that never waits for a
+frame (SpeculativeRenderer).
+
+  [REF eval.py:75-118]     render_video          (+ utils/camera_utils.py:20-70, 269-276: lerp, slerp, interpolation_pose)
+  [REF eval.py:159-190]    render_trainSequence
+  [REF eval.py:192-226]    render_set
+  [REF eval.py:110,155,182,217]   torchvision.utils.save_image per frame -> one PngWriter.submit per ring of frames
+
+The reference muxes the video frames into an mp4 with cv2 [REF eval.py:113-115]; neither cv2 nor ffmpeg exists here, so render_video
+stops at the numbered frames in renders_video/ and returns their count.  The files: eval/<name>/ours_<iteration>/{renders, gt}/%05d.png,
+renders/view_%03d/%05d.png, renders_video/%05d.png -- the trees `metrics.evaluate_dirs` scores."""
+from __future__ import annotations
+
+import os
+import time as _time
+
+import numpy as np
+import torch
+
+from .cameras import Camera
+from .png_ops import PngWriter
+
+DOT_THRESHOLD = 0.9995
+
+
+def slerp(t, q0, q1):
+    """The reference's slerp [REF utils/camera_utils.py:26-70] on the host, in the inputs' precision: the angle comes from the
+    normalised inputs, the weights multiply the inputs AS GIVEN, there is no shortest-arc flip, and above |dot| 0.9995 the result is
+    the plain lerp of the un-normalised inputs.  numpy arrays or CPU tensors in, a numpy array out."""
+    a = q0.detach().cpu().numpy() if torch.is_tensor(q0) else np.asarray(q0)
+    b = q1.detach().cpu().numpy() if torch.is_tensor(q1) else np.asarray(q1)
+    cos_angle = np.sum((a / np.linalg.norm(a)) * (b / np.linalg.norm(b)))
+    if np.abs(cos_angle) > DOT_THRESHOLD:
+        return (1 - t) * a + t * b
+    angle = np.arccos(cos_angle)
+    return (np.sin(angle - angle * t) / np.sin(angle)) * a + (np.sin(angle * t) / np.sin(angle)) * b
+
+
+def interpolation_pose(view, previous_view, ratio):
+    """(new_T, new_R) between previous_view (ratio 0) and view (ratio 1) [REF utils/camera_utils.py:269-276]: the translation
+    interpolated linearly, the rotation by slerp of the two matrices' quaternions (pytorch3d.transforms: this repository's shim)."""
+    from pytorch3d.transforms import matrix_to_quaternion, quaternion_to_matrix
+    t, pre_t = np.asarray(view.T), np.asarray(previous_view.T)
+    new_t = pre_t + (t - pre_t) * ratio
+    quat = matrix_to_quaternion(torch.from_numpy(np.asarray(view.R)))
+    pre_quat = matrix_to_quaternion(torch.from_numpy(np.asarray(previous_view.R)))
+    new_quat = torch.from_numpy(np.asarray(slerp(ratio, pre_quat, quat)))
+    new_R = quaternion_to_matrix(new_quat[None]).squeeze().cpu().numpy()
+    return new_t, new_R
+
+
+def video_schedule(n_views, interpolation, step):
+    """The frames render_video walks, as (frame_id, previous_index, view_index, ratio) [REF eval.py:81-112]: view 0 gives the one
+    frame 0; view idx with idx % step == 0 gives `interpolation` frames between view idx - step and itself, numbered
+    frame + (idx // step - 1) * interpolation for frame = 1 .. interpolation.  interpolation * ((n_views - 1) // step) + 1 in all."""
+    n_views, interpolation, step = int(n_views), int(interpolation), int(step)
+    if n_views < 1 or interpolation < 1 or step < 1:
+        raise ValueError(f"video_schedule: n_views = {n_views}, interpolation = {interpolation}, step = {step} must all be >= 1")
+    frames = [(0, 0, 0, 1 / interpolation)]
+    for idx in range(step, n_views, step):
+        for frame in range(1, interpolation + 1):
+            frames.append((frame + (idx // step - 1) * interpolation, idx - step, idx, frame / interpolation))
+    return frames
+
+
+def _cam(view):
+    return view["cam"] if isinstance(view, dict) else view          # (optical-flow datasets wrap the camera)
+
+
+def _time_of(view, dev):
+    return torch.as_tensor(np.asarray(view.time), dtype=torch.float32).reshape(-1)[:1].to(dev)
+
+
+def _run(frames, gaussians, pipeline, background, iteration, writer, renderer):
+    """Render `frames` -- an iterable of (camera, time tensor, render file, gt image or None, gt file) -- through a
+    SpeculativeRenderer; after every ring's flush() (the images are final then: overflowed frames were replaced in place) the ring's
+    images go to ONE writer.submit, its ground truths to a second.  Returns the statistics dictionary."""
+    from .renderer import SpeculativeRenderer
+    sr = renderer if renderer is not None else SpeculativeRenderer(gaussians, pipeline, background)
+    own = writer is None
+    w = PngWriter() if own else writer
+    sr.flush()
+    ring, count, again = [], 0, 0
+
+    def close_ring():
+        nonlocal ring, again
+        again += sr.flush()
+        if ring:
+            w.submit([im for im, _, _, _ in ring], [p for _, p, _, _ in ring])
+            gts = [(gt, gp) for _, _, gt, gp in ring if gt is not None]
+            if gts:
+                w.submit([gt for gt, _ in gts], [gp for _, gp in gts])
+        ring = []
+
+    torch.cuda.synchronize(background.device)
+    start = _time.perf_counter()
+    try:
+        with torch.no_grad():
+            for cam, time_, path, gt, gt_path in frames:
+                if len(ring) >= sr.slots:
+                    close_ring()
+                image = sr(cam, time=time_, it=iteration)["render"]
+                ring.append((image, path, gt[0:3].to(image.device) if gt is not None else None, gt_path))
+                count += 1
+            close_ring()
+        if own:
+            w.close()
+        else:
+            torch.cuda.synchronize(background.device)       # (a caller's writer: its files are complete after its close())
+    except BaseException:
+        if own:
+            try:
+                w.close()
+            except BaseException:       # noqa: BLE001  (the loop's own exception wins)
+                pass
+        raise
+    seconds = _time.perf_counter() - start
+    return {"frames": count, "seconds": seconds, "views_per_s": count / seconds if seconds > 0 else float("inf"), "rerendered": again}
+
+
+def render_set(model_path, name, iteration, views, gaussians, pipeline, background, args=None, writer=None, renderer=None):
+    """Every view at its own time to eval/<name>/ours_<iteration>/renders/%05d.png, its ground truth (`original_image`) to gt/
+    [REF eval.py:192-226]; the keypoints to <model_path>/kpts_fps.txt (the first args.max_points) and, with args.adaptive_points_num > 0,
+    kpts_incre.txt (the rest).  `args` defaults to the model's own.  writer: a PngWriter of the caller's (it closes it); renderer: a
+    SpeculativeRenderer to keep its capacity across calls.  Returns (eval_path, {"frames", "seconds", "views_per_s", "rerendered"})."""
+    eval_path = os.path.join(model_path, "eval", name)
+    render_path = os.path.join(eval_path, "ours_{}".format(iteration), "renders")
+    gts_path = os.path.join(eval_path, "ours_{}".format(iteration), "gt")
+    os.makedirs(render_path, exist_ok=True)
+    os.makedirs(gts_path, exist_ok=True)
+    args = args if args is not None else getattr(gaussians, "args", None)
+    kpts = getattr(gaussians, "get_superGaussians", None)
+    if kpts is not None:
+        kpts = kpts.detach().cpu().numpy()
+        max_points = int(getattr(args, "max_points", kpts.shape[0]))
+        np.savetxt(os.path.join(model_path, "kpts_fps.txt"), kpts[:max_points])
+        if getattr(args, "adaptive_points_num", 0) > 0:
+            np.savetxt(os.path.join(model_path, "kpts_incre.txt"), kpts[max_points:])
+    dev = background.device
+    views = [_cam(v) for v in views]
+    frames = ((v, _time_of(v, dev), os.path.join(render_path, "{0:05d}.png".format(i)), v.original_image,
+               os.path.join(gts_path, "{0:05d}.png".format(i))) for i, v in enumerate(views))
+    return eval_path, _run(frames, gaussians, pipeline, background, iteration, writer, renderer)
+
+
+def render_trainSequence(model_path, name, iteration, train_views, gaussians, pipeline, background, test_views, freeze_view_number=5,
+                         writer=None, renderer=None):
+    """The frozen test view `freeze_view_number` at every training view's time to renders/view_%03d/%05d.png, the training views'
+    ground truth to gt/ [REF eval.py:159-190].  Returns (eval_path, statistics)."""
+    eval_path = os.path.join(model_path, "eval", name)
+    render_path = os.path.join(eval_path, "ours_{}".format(iteration), "renders", f"view_{freeze_view_number:03d}")
+    gts_path = os.path.join(eval_path, "ours_{}".format(iteration), "gt")
+    os.makedirs(render_path, exist_ok=True)
+    os.makedirs(gts_path, exist_ok=True)
+    dev = background.device
+    view_freeze = _cam(test_views[freeze_view_number])
+    train_views = [_cam(v) for v in train_views]
+    frames = ((view_freeze, _time_of(v, dev), os.path.join(render_path, "{0:05d}.png".format(i)), v.original_image,
+               os.path.join(gts_path, "{0:05d}.png".format(i))) for i, v in enumerate(train_views))
+    return eval_path, _run(frames, gaussians, pipeline, background, iteration, writer, renderer)
+
+
+def render_video(model_path, name, iteration, views, gaussians, pipeline, background, interpolation=5, step=None, writer=None,
+                 renderer=None):
+    """The frames of `video_schedule` -- poses and times interpolated between neighbouring views -- to renders_video/%05d.png
+    [REF eval.py:75-118]; step defaults to the reference's 2 for a "vrig" model path, else 1.  No mp4 is made (module docstring).
+    Returns (eval_path, statistics)."""
+    eval_path = os.path.join(model_path, "eval", name)
+    render_path = os.path.join(eval_path, "ours_{}".format(iteration), "renders_video")
+    os.makedirs(render_path, exist_ok=True)
+    if step is None:
+        step = 2 if "vrig" in model_path else 1
+    dev = background.device
+    views = [_cam(v) for v in views]
+
+    def frames():
+        for frame_id, pi, vi, ratio in video_schedule(len(views), interpolation, step):
+            view, previous = views[vi], views[pi]
+            t1, t0 = _time_of(view, "cpu"), _time_of(previous, "cpu")              # (float32 on the host: no read of the device)
+            time_inter = t0 + round(ratio * interpolation) * ((t1 - t0) / interpolation)        # previous + frame * time_slice
+            new_t, new_R = interpolation_pose(view, previous, ratio)
+            cam = Camera(R=new_R, T=new_t, FoVx=previous.FoVx, FoVy=previous.FoVy, width=previous.image_width, height=previous.image_height,
+                         time=float(time_inter), device=dev, uid=getattr(previous, "uid", 0))
+            yield cam, time_inter.to(dev), os.path.join(render_path, "{0:05d}.png".format(frame_id)), None, None
+
+    return eval_path, _run(frames(), gaussians, pipeline, background, iteration, writer, renderer)

@@ -394,7 +394,7 @@ def _save_png(image, path):
 
 @torch.no_grad()
 def render_kpts(views, gaussians, pipeline, background, kpts, kpts_rotation, iteration, metrics=False, view_id=None, out_dir=None,
-                delta=None):
+                delta=None, writer=None):
     """Render every predicted frame: frame i's per-keypoint delta (kpts[i] - super_gaussians, kpts_rotation[i]) goes through the SPARSE
     blend (KeypointBlend, gp_blend_forward) with the weights and neighbour indices of ONE forward at views[0].time, then through
     render_motion with that forward's lifecycle opacity.  The reference multiplies two dense [N, K] weight matrices per frame
@@ -402,7 +402,9 @@ def render_kpts(views, gaussians, pipeline, background, kpts, kpts_rotation, ite
     `delta` [F, K, 7] (GCN_xyzr.rollout's third output) replaces the subtraction and concatenation.
     View of frame i: views[i] with `metrics`, views[view_id] with `view_id`, else the reference's back-and-forth sweep over the first
     half of the views (its formula reads the builtin `id`; the frame index is what it means).
-    Returns the list of images [3, H, W]; with out_dir also writes <out_dir>/renders[/view<id>]/%05d.png (and gt/ with metrics)."""
+    Returns the list of images [3, H, W]; with out_dir also writes <out_dir>/renders[/view<id>]/%05d.png (and gt/ with metrics).
+    writer: a png_ops.PngWriter; the files are then encoded on the device and written behind the loop (complete after the caller's
+    writer.close()) instead of through the host encoder, frame by frame."""
     from .deform_ops import KeypointBlend
     from .renderer import render_motion
     dev = gaussians.get_xyz.device
@@ -421,6 +423,7 @@ def render_kpts(views, gaussians, pipeline, background, kpts, kpts_rotation, ite
             gts_path = os.path.join(out_dir, "gt")
             os.makedirs(gts_path, exist_ok=True)
     images = []
+    save = _save_png if writer is None else writer.submit
     n = len(delta) if delta is not None else len(kpts)
     for i in range(n):
         d = delta[i] if delta is not None else torch.cat([kpts[i] - base, kpts_rotation[i]], dim=-1)
@@ -428,7 +431,7 @@ def render_kpts(views, gaussians, pipeline, background, kpts, kpts_rotation, ite
         if metrics:
             view = views[i]
             if gts_path is not None:
-                _save_png(view.original_image[0:3, :, :], os.path.join(gts_path, '{0:05d}'.format(i) + ".png"))
+                save(view.original_image[0:3, :, :], os.path.join(gts_path, '{0:05d}'.format(i) + ".png"))
         elif view_id is not None:
             view = views[view_id]
         else:
@@ -437,6 +440,6 @@ def render_kpts(views, gaussians, pipeline, background, kpts, kpts_rotation, ite
             view = views[(i % half) * position]
         rendering = render_motion(view, gaussians, pipeline, background, xyz_t=xyz_final, r_t=delta_r, opacity=life_opacity)["render"]
         if render_path is not None:
-            _save_png(rendering, os.path.join(render_path, '{0:05d}'.format(i) + ".png"))
+            save(rendering, os.path.join(render_path, '{0:05d}'.format(i) + ".png"))
         images.append(rendering)
     return images
