@@ -64,16 +64,20 @@ struct PngFilterShared {
     int ftype;
 };
 
-PNG_FN int png_q8(const PngPlan& p, int b, int c, int y, int x) {
-    const size_t i = (((size_t)b * 3 + c) * p.H + y) * p.W + x;
-    if (p.src_kind == GP_PNG_SRC_U8) return ((const uint8_t*)p.src)[i];
-    const float v = ((const float*)p.src)[i];
+// element i of `src` as 8 bits (the JPEG encoder's jpeg_core.h reads its pixels through this too)
+PNG_FN int png_q8_at(const void* src, int src_kind, size_t i) {
+    if (src_kind == GP_PNG_SRC_U8) return ((const uint8_t*)src)[i];
+    const float v = ((const float*)src)[i];
 #if defined(__HIPCC__)
     const float s = __fadd_rn(__fmul_rn(v, 255.f), 0.5f);
 #else
     const float s = v * 255.f + 0.5f;
 #endif
     return (int)fminf(fmaxf(floorf(s), 0.f), 255.f);      // (fmaxf(NaN, 0) = 0)
+}
+
+PNG_FN int png_q8(const PngPlan& p, int b, int c, int y, int x) {
+    return png_q8_at(p.src, p.src_kind, (((size_t)b * 3 + c) * p.H + y) * p.W + x);
 }
 
 PNG_FN int png_paeth(int a, int b, int c) {

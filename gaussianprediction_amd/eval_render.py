@@ -1,15 +1,17 @@
 """The render-to-disk loops of the reference's eval.py: the test views, a frozen-view sequence over the training times, and the
 interpolated-pose video frames, written as PNG files encoded on the device (png_ops) behind a render loop that never waits for a
-frame (SpeculativeRenderer).
+frame (SpeculativeRenderer); on request the video frames also go into a Motion-JPEG video encoded on the device (jpeg_ops).
 
   [REF eval.py:75-118]     render_video          (+ utils/camera_utils.py:20-70, 269-276: lerp, slerp, interpolation_pose)
   [REF eval.py:159-190]    render_trainSequence
   [REF eval.py:192-226]    render_set
   [REF eval.py:110,155,182,217]   torchvision.utils.save_image per frame -> one PngWriter.submit per ring of frames
 
-The reference muxes the video frames into an mp4 with cv2 [REF eval.py:113-115]; neither cv2 nor ffmpeg exists here, so render_video
-stops at the numbered frames in renders_video/ and returns their count.  The files: eval/<name>/ours_<iteration>/{renders, gt}/%05d.png,
-renders/view_%03d/%05d.png, renders_video/%05d.png -- the trees `metrics.evaluate_dirs` scores."""
+The reference muxes the video frames into an mp4 with cv2 [REF eval.py:113-115]; neither cv2 nor ffmpeg exists here, so by default
+render_video stops at the numbered frames in renders_video/ and returns their count, and with `video=` it writes the reference's
+file name with another container beside that directory: ours_<iteration>/<scene>.avi, Motion-JPEG from jpeg_ops.VideoWriter.  The
+files: eval/<name>/ours_<iteration>/{renders, gt}/%05d.png, renders/view_%03d/%05d.png, renders_video/%05d.png -- the trees
+`metrics.evaluate_dirs` scores."""
 from __future__ import annotations
 
 import os
@@ -72,10 +74,11 @@ def _time_of(view, dev):
     return torch.as_tensor(np.asarray(view.time), dtype=torch.float32).reshape(-1)[:1].to(dev)
 
 
-def _run(frames, gaussians, pipeline, background, iteration, writer, renderer):
+def _run(frames, gaussians, pipeline, background, iteration, writer, renderer, video=None):
     """Render `frames` -- an iterable of (camera, time tensor, render file, gt image or None, gt file) -- through a
     SpeculativeRenderer; after every ring's flush() (the images are final then: overflowed frames were replaced in place) the ring's
-    images go to ONE writer.submit, its ground truths to a second.  Returns the statistics dictionary."""
+    images go to ONE writer.submit, its ground truths to a second; video: a jpeg_ops.VideoWriter that takes the ring's images too
+    (closed here).  Returns the statistics dictionary."""
     from .renderer import SpeculativeRenderer
     sr = renderer if renderer is not None else SpeculativeRenderer(gaussians, pipeline, background)
     own = writer is None
@@ -88,6 +91,8 @@ def _run(frames, gaussians, pipeline, background, iteration, writer, renderer):
         again += sr.flush()
         if ring:
             w.submit([im for im, _, _, _ in ring], [p for _, p, _, _ in ring])
+            if video is not None:
+                video.submit([im for im, _, _, _ in ring])
             gts = [(gt, gp) for _, _, gt, gp in ring if gt is not None]
             if gts:
                 w.submit([gt for gt, _ in gts], [gp for _, gp in gts])
@@ -108,7 +113,14 @@ def _run(frames, gaussians, pipeline, background, iteration, writer, renderer):
             w.close()
         else:
             torch.cuda.synchronize(background.device)       # (a caller's writer: its files are complete after its close())
+        if video is not None:
+            video.close()
     except BaseException:
+        if video is not None:
+            try:
+                video.close()
+            except BaseException:       # noqa: BLE001  (the loop's own exception wins)
+                pass
         if own:
             try:
                 w.close()
@@ -162,10 +174,12 @@ def render_trainSequence(model_path, name, iteration, train_views, gaussians, pi
 
 
 def render_video(model_path, name, iteration, views, gaussians, pipeline, background, interpolation=5, step=None, writer=None,
-                 renderer=None):
+                 renderer=None, video=None, fps=120):
     """The frames of `video_schedule` -- poses and times interpolated between neighbouring views -- to renders_video/%05d.png
-    [REF eval.py:75-118]; step defaults to the reference's 2 for a "vrig" model path, else 1.  No mp4 is made (module docstring).
-    Returns (eval_path, statistics)."""
+    [REF eval.py:75-118]; step defaults to the reference's 2 for a "vrig" model path, else 1.  video: True for
+    ours_<iteration>/<basename(dirname(model_path))>.avi -- the reference's name [REF eval.py:113] with the container's extension,
+    beside renders_video/ -- or a path; the frames then also go, in order, into a Motion-JPEG video at `fps` (the reference's 120),
+    encoded on the device, and the statistics gain "video": its path.  Returns (eval_path, statistics)."""
     eval_path = os.path.join(model_path, "eval", name)
     render_path = os.path.join(eval_path, "ours_{}".format(iteration), "renders_video")
     os.makedirs(render_path, exist_ok=True)
@@ -184,4 +198,11 @@ def render_video(model_path, name, iteration, views, gaussians, pipeline, backgr
                          time=float(time_inter), device=dev, uid=getattr(previous, "uid", 0))
             yield cam, time_inter.to(dev), os.path.join(render_path, "{0:05d}.png".format(frame_id)), None, None
 
-    return eval_path, _run(frames(), gaussians, pipeline, background, iteration, writer, renderer)
+    if video is None or video is False:
+        return eval_path, _run(frames(), gaussians, pipeline, background, iteration, writer, renderer)
+    from .jpeg_ops import VideoWriter
+    video_path = (os.path.join(eval_path, "ours_{}".format(iteration), os.path.basename(os.path.dirname(model_path)) + ".avi")
+                  if video is True else os.fspath(video))
+    stats = _run(frames(), gaussians, pipeline, background, iteration, writer, renderer, video=VideoWriter(video_path, fps))
+    stats["video"] = video_path
+    return eval_path, stats

@@ -225,12 +225,14 @@ def _lpips_from(weights, device):
     return [_lp.cached(net, device, os.fspath(weights)) for net in ("vgg", "alex")]
 
 
-def evaluate_dirs(path, device="cuda", write=True, lpips_weights=None):
+def evaluate_dirs(path, device="cuda", write=True, lpips_weights=None, device_jpeg=False):
     """The directory form of the reference's metrics.py [REF metrics.py:113-178]: for every `<path>/<method>/` holding `renders/`
     and `gt/`, score the sorted image pairs (files whose name contains "depth" are skipped), write `<method>/deltas/%05d.jpg` and
     -- as the reference does -- `<path>/results.json` and `<path>/per_view.json` of the last method.  Keys: SSIM, PSNR, MS-SSIM,
     D-SSIM; with `lpips_weights` (a directory holding the weight files find_lpips_weights names, or a dict {"vgg": ..., "alex": ...})
     the reference's six in its order: SSIM, PSNR, LPIPS-vgg, LPIPS-alex, MS-SSIM, D-SSIM.  The images were saved as 8 bits already, so nothing is quantised again.  One table read per method.
+    device_jpeg: the deltas images are encoded on the device (jpeg_ops.JpegWriter at quality 75, 4:2:0 -- the defaults of the host
+    encoder the default path uses) and written behind the loop, instead of one read and one host encode per image.
     Returns {method: {"summary": ..., "per_view": ...}} with the dictionaries that were written."""
     from PIL import Image
     device = torch.device(device)
@@ -250,16 +252,24 @@ def evaluate_dirs(path, device="cuda", write=True, lpips_weights=None):
         if write:
             os.makedirs(os.path.join(mdir, "deltas"), exist_ok=True)
         pending = []
+        jw = None
+        if write and device_jpeg:
+            from .jpeg_ops import JpegWriter
+            jw = JpegWriter(quality=75, subsampling="420")
         for i, (rn, gn) in enumerate(zip(rnames, gnames)):
             render, gt = _load_rgb(os.path.join(rdir, rn), device), _load_rgb(os.path.join(gdir, gn), device)
             r = image_metrics(render, gt, out=table[i:i + 1], deltas=write)
             for net, lt in zip(nets, ltabs):
                 net(render, gt, out=lt[i:i + 1])
-            if write:
+            if jw is not None:
+                jw.submit(r.deltas.permute(0, 3, 1, 2), [os.path.join(mdir, "deltas", "{0:05d}.jpg".format(i))])
+            elif write:
                 pending.append(r.deltas)
         h = table.cpu() if not nets else torch.cat([table] + [lt[:, :1] for lt in ltabs], dim=1).cpu()      # (one read either way)
         for i, d in enumerate(pending):
             Image.fromarray(d[0].cpu().numpy()).save(os.path.join(mdir, "deltas", "{0:05d}.jpg".format(i)))
+        if jw is not None:
+            jw.close()
         cols = {"SSIM": SSIM, "PSNR": PSNR}
         cols.update({f"LPIPS-{net.net_type}": METRIC_COUNT + k for k, net in enumerate(nets)})
         cols.update({"MS-SSIM": MS_SSIM, "D-SSIM": D_SSIM})

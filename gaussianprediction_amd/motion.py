@@ -394,7 +394,7 @@ def _save_png(image, path):
 
 @torch.no_grad()
 def render_kpts(views, gaussians, pipeline, background, kpts, kpts_rotation, iteration, metrics=False, view_id=None, out_dir=None,
-                delta=None, writer=None):
+                delta=None, writer=None, video=None, fps=10):
     """Render every predicted frame: frame i's per-keypoint delta (kpts[i] - super_gaussians, kpts_rotation[i]) goes through the SPARSE
     blend (KeypointBlend, gp_blend_forward) with the weights and neighbour indices of ONE forward at views[0].time, then through
     render_motion with that forward's lifecycle opacity.  The reference multiplies two dense [N, K] weight matrices per frame
@@ -404,7 +404,9 @@ def render_kpts(views, gaussians, pipeline, background, kpts, kpts_rotation, ite
     half of the views (its formula reads the builtin `id`; the frame index is what it means).
     Returns the list of images [3, H, W]; with out_dir also writes <out_dir>/renders[/view<id>]/%05d.png (and gt/ with metrics).
     writer: a png_ops.PngWriter; the files are then encoded on the device and written behind the loop (complete after the caller's
-    writer.close()) instead of through the host encoder, frame by frame."""
+    writer.close()) instead of through the host encoder, frame by frame.
+    video: True for <out_dir>/renders[/view<id>]/video.avi [REF train_GCN.py:45-53: renders/video.mp4 at 10 fps], or a path: the
+    renderings then also go into a Motion-JPEG video at `fps`, encoded on the device (jpeg_ops.VideoWriter), complete on return."""
     from .deform_ops import KeypointBlend
     from .renderer import render_motion
     dev = gaussians.get_xyz.device
@@ -423,23 +425,35 @@ def render_kpts(views, gaussians, pipeline, background, kpts, kpts_rotation, ite
             gts_path = os.path.join(out_dir, "gt")
             os.makedirs(gts_path, exist_ok=True)
     images = []
+    vw = None
+    if video is not None and video is not False:
+        from .jpeg_ops import VideoWriter
+        if video is True and render_path is None:
+            raise ValueError("render_kpts: video=True needs out_dir (or pass the video's path)")
+        vw = VideoWriter(os.path.join(render_path, "video.avi") if video is True else os.fspath(video), fps)
     save = _save_png if writer is None else writer.submit
     n = len(delta) if delta is not None else len(kpts)
-    for i in range(n):
-        d = delta[i] if delta is not None else torch.cat([kpts[i] - base, kpts_rotation[i]], dim=-1)
-        xyz_final, delta_r = KeypointBlend.apply(d.contiguous(), raw_w, knn_idx, gaussians._xyz.detach(), gaussians._rotation.detach(), False)
-        if metrics:
-            view = views[i]
-            if gts_path is not None:
-                save(view.original_image[0:3, :, :], os.path.join(gts_path, '{0:05d}'.format(i) + ".png"))
-        elif view_id is not None:
-            view = views[view_id]
-        else:
-            half = max(len(views) // 2, 1)
-            position = 2 if ((i // half) % 2 == 0) else -2
-            view = views[(i % half) * position]
-        rendering = render_motion(view, gaussians, pipeline, background, xyz_t=xyz_final, r_t=delta_r, opacity=life_opacity)["render"]
-        if render_path is not None:
-            save(rendering, os.path.join(render_path, '{0:05d}'.format(i) + ".png"))
-        images.append(rendering)
+    try:
+        for i in range(n):
+            d = delta[i] if delta is not None else torch.cat([kpts[i] - base, kpts_rotation[i]], dim=-1)
+            xyz_final, delta_r = KeypointBlend.apply(d.contiguous(), raw_w, knn_idx, gaussians._xyz.detach(), gaussians._rotation.detach(), False)
+            if metrics:
+                view = views[i]
+                if gts_path is not None:
+                    save(view.original_image[0:3, :, :], os.path.join(gts_path, '{0:05d}'.format(i) + ".png"))
+            elif view_id is not None:
+                view = views[view_id]
+            else:
+                half = max(len(views) // 2, 1)
+                position = 2 if ((i // half) % 2 == 0) else -2
+                view = views[(i % half) * position]
+            rendering = render_motion(view, gaussians, pipeline, background, xyz_t=xyz_final, r_t=delta_r, opacity=life_opacity)["render"]
+            if render_path is not None:
+                save(rendering, os.path.join(render_path, '{0:05d}'.format(i) + ".png"))
+            images.append(rendering)
+            if vw is not None and (len(images) % vw.slots == 0 or i == n - 1):
+                vw.submit(images[len(images) - 1 - (len(images) - 1) % vw.slots:])       # (a ring of frames per encode)
+    finally:
+        if vw is not None:
+            vw.close()
     return images

@@ -156,7 +156,7 @@ class PngWriter:
     def _start(self):
         if not self._workers:
             for k in range(self.threads):
-                w = threading.Thread(target=self._work, name=f"PngWriter-{k}", daemon=True)
+                w = threading.Thread(target=self._work, name=f"{type(self).__name__}-{k}", daemon=True)
                 w.start()
                 self._workers.append(w)
 
@@ -169,8 +169,7 @@ class PngWriter:
             try:
                 if self._error is None:
                     event.synchronize()
-                    with open(path, "wb") as fp:
-                        fp.write(memoryview(self._pinned[slot].numpy())[:int(sizes[index])])
+                    self._store(path, memoryview(self._pinned[slot].numpy())[:int(sizes[index])])
             except BaseException as e:          # noqa: BLE001  (kept for close())
                 with self._cond:
                     if self._error is None:
@@ -179,6 +178,14 @@ class PngWriter:
                 with self._cond:
                     self._free.append(slot)
                     self._cond.notify_all()
+
+    def _encode(self, x):
+        """(buffer, sizes) of the batch x; jpeg_ops' writers put their own encoder behind the same ring."""
+        return encode(x)
+
+    def _store(self, path, data):
+        with open(path, "wb") as fp:
+            fp.write(data)
 
     def _take(self, n):
         with self._cond:
@@ -200,7 +207,7 @@ class PngWriter:
         paths = [paths] if isinstance(paths, (str, bytes)) or hasattr(paths, "__fspath__") else list(paths)
         if len(paths) != x.shape[0]:
             raise RuntimeError(f"PngWriter.submit: {x.shape[0]} images but {len(paths)} paths")
-        out, sizes = encode(x)
+        out, sizes = self._encode(x)
         B, stride = out.shape
         if self._pinned is None or self._pinned.shape[1] < stride:
             self._drain()                       # (a larger image than any before: the buffers are replaced once nothing is in flight)
