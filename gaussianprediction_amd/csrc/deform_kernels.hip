@@ -798,12 +798,16 @@ __device__ __forceinline__ void normalize_bwd(const float* v, const float* g, fl
 // about one lane per clock, so instead of 7 atomics per (Gaussian, neighbour) each 256-Gaussian chunk is
 // COUNTING-SORTED by keypoint in LDS (integer atomics only, for the ranks) and every keypoint's owner thread sums
 // its own contiguous list into a plain LDS accumulator: no floating-point atomics, deterministic per workgroup.
+// (The ranks must not depend on which wave's atomic lands first, or the list order -- and with it the last bits of the sum -- changes
+// from launch to launch: a keypoint's counter holds one BYTE per wave of the workgroup (a wave adds at most 64 entries to a keypoint,
+// its 64 Gaussians have distinct neighbours), a wave's rank is its own byte, and a list is wave 0's entries, then wave 1's, ...)
 // The normalisation Jacobian of a keypoint's quaternion is linear in the incoming gradient, so it is applied once
 // per (workgroup, keypoint) after the sum.  Workgroup partials go to `partial`; gp_blend_bwd_reduce_kernel adds them.
 //
 // dynamic LDS: acc[K*7] | delta[K*od] | cnt[K] | base[K+1] | g[7*256] | inv[K] | w[256*2*nn] | sorted u16 [256*nn]
 #define BB_LONG 20          // a keypoint's list beyond this length is summed by a wave (mean length = nn)
 #define BB_LONG_CAP 320     // >= 256 * GP_MAX_NN / (BB_LONG + 1) lists can be that long
+__device__ __forceinline__ int bb_count(int c) { return (c & 255) + ((c >> 8) & 255) + ((c >> 16) & 255) + ((c >> 24) & 255); }   // entries of all four waves
 template <int NN, bool I16 = false>
 __device__ __forceinline__ void blend_bwd_body(BlendDev a, const float* __restrict__ g_xyz_t,
                                                const float* __restrict__ g_q_t, float* __restrict__ g_delta,
@@ -815,6 +819,7 @@ __device__ __forceinline__ void blend_bwd_body(BlendDev a, const float* __restri
     const int nn = NN > 0 ? NN : a.nn;
     const int K = (int)a.K;
     const int tid = threadIdx.x;
+    const int wsh = (tid >> 6) * 8;                     // this wave's byte of a keypoint's counter
     float* s_acc = s_dyn;                               // [K*7]
     float* s_delta = s_acc + (nn > 0 ? K * 7 : 0);      // [K*od]
     int* s_cnt = (int*)(s_delta + (nn > 0 ? K * od : 0));   // [K]
@@ -915,7 +920,7 @@ __device__ __forceinline__ void blend_bwd_body(BlendDev a, const float* __restri
                     sr += wr[k] * gwr[k];
                     s_w[k * 256 + tid] = wx[k];
                     s_w[(nn + k) * 256 + tid] = wr[k];
-                    rk[k] = atomicAdd(&s_cnt[kps[k]], 1);          // rank of this entry within its keypoint
+                    rk[k] = (atomicAdd(&s_cnt[kps[k]], 1 << wsh) >> wsh) & 255;     // rank of this entry among its WAVE's entries of the keypoint
                 }
                 if (g_raw_w) {        // (NULL: the weights are inputs without a gradient, 8 nn bytes per Gaussian not written)
                     if constexpr (NN > 0) {
@@ -951,7 +956,7 @@ __device__ __forceinline__ void blend_bwd_body(BlendDev a, const float* __restri
                 const int per = (K + 255) / 256;
                 const int b0 = tid * per;
                 int loc = 0;
-                for (int e = 0; e < per; ++e) if (b0 + e < K) loc += s_cnt[b0 + e];
+                for (int e = 0; e < per; ++e) if (b0 + e < K) loc += bb_count(s_cnt[b0 + e]);
                 int inc = loc;
                 inc = gp_wave_scan_add(inc);
                 if ((tid & 63) == 63) s_wsum[tid >> 6] = inc;
@@ -959,13 +964,14 @@ __device__ __forceinline__ void blend_bwd_body(BlendDev a, const float* __restri
                 int woff = 0;
                 for (int w = 0; w < (tid >> 6); ++w) woff += s_wsum[w];
                 int run = woff + inc - loc;
-                for (int e = 0; e < per; ++e) if (b0 + e < K) { s_base[b0 + e] = run; run += s_cnt[b0 + e]; }
+                for (int e = 0; e < per; ++e) if (b0 + e < K) { s_base[b0 + e] = run; run += bb_count(s_cnt[b0 + e]); }
                 if (tid == 255) s_base[K] = run;
             }
             __syncthreads();
             if (live) {
 #pragma unroll
-                for (int k = 0; k < nn; ++k) s_sorted[s_base[kps[k]] + rk[k]] = (unsigned short)((k << 8) | tid);
+                for (int k = 0; k < nn; ++k)          // behind the entries of the waves in front of this one
+                    s_sorted[s_base[kps[k]] + bb_count(s_cnt[kps[k]] & ((1 << wsh) - 1)) + rk[k]] = (unsigned short)((k << 8) | tid);
             }
             __syncthreads();
             for (int kp = tid; kp < K; kp += 256) {
