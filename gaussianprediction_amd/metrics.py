@@ -225,7 +225,33 @@ def _lpips_from(weights, device):
     return [_lp.cached(net, device, os.fspath(weights)) for net in ("vgg", "alex")]
 
 
-def evaluate_dirs(path, device="cuda", write=True, lpips_weights=None, device_jpeg=False):
+def _score_decoded_groups(rdir, gdir, rnames, gnames, mdir, device, table, nets, ltabs, write, jw, pending, group):
+    """evaluate_dirs' loop with device_png: `group` pairs per png_decode.decode_files call (float32, the first three channels), and
+    one batched image_metrics call per run of pairs of one shape."""
+    from . import png_decode
+    for lo in range(0, len(rnames), group):
+        hi = min(len(rnames), lo + group)
+        imgs = png_decode.decode_files([os.path.join(rdir, n) for n in rnames[lo:hi]] + [os.path.join(gdir, n) for n in gnames[lo:hi]],
+                                       device=device, dtype=torch.float32, channels=3)
+        renders, gts = imgs[:hi - lo], imgs[hi - lo:]
+        i = lo
+        while i < hi:
+            j = i + 1
+            while j < hi and renders[j - lo].shape == renders[i - lo].shape and gts[j - lo].shape == gts[i - lo].shape:
+                j += 1
+            render, gt = torch.stack(renders[i - lo:j - lo]), torch.stack(gts[i - lo:j - lo])
+            r = image_metrics(render, gt, out=table[i:j], deltas=write)
+            for k in range(i, j):
+                for net, lt in zip(nets, ltabs):
+                    net(render[k - i:k - i + 1], gt[k - i:k - i + 1], out=lt[k:k + 1])
+            if jw is not None:
+                jw.submit(r.deltas.permute(0, 3, 1, 2), [os.path.join(mdir, "deltas", "{0:05d}.jpg".format(k)) for k in range(i, j)])
+            elif write:
+                pending += [r.deltas[k - i:k - i + 1] for k in range(i, j)]
+            i = j
+
+
+def evaluate_dirs(path, device="cuda", write=True, lpips_weights=None, device_jpeg=False, device_png=False, png_group=16):
     """The directory form of the reference's metrics.py [REF metrics.py:113-178]: for every `<path>/<method>/` holding `renders/`
     and `gt/`, score the sorted image pairs (files whose name contains "depth" are skipped), write `<method>/deltas/%05d.jpg` and
     -- as the reference does -- `<path>/results.json` and `<path>/per_view.json` of the last method.  Keys: SSIM, PSNR, MS-SSIM,
@@ -233,6 +259,9 @@ def evaluate_dirs(path, device="cuda", write=True, lpips_weights=None, device_jp
     the reference's six in its order: SSIM, PSNR, LPIPS-vgg, LPIPS-alex, MS-SSIM, D-SSIM.  The images were saved as 8 bits already, so nothing is quantised again.  One table read per method.
     device_jpeg: the deltas images are encoded on the device (jpeg_ops.JpegWriter at quality 75, 4:2:0 -- the defaults of the host
     encoder the default path uses) and written behind the loop, instead of one read and one host encode per image.
+    device_png: the image pairs are decoded on the device (png_decode.decode_files: float32, the first three channels), `png_group`
+    pairs per call, and every run of equal-shaped pairs of a group is scored by one batched image_metrics call, instead of one host
+    decode per file; the numbers are the same.
     Returns {method: {"summary": ..., "per_view": ...}} with the dictionaries that were written."""
     from PIL import Image
     device = torch.device(device)
@@ -257,6 +286,8 @@ def evaluate_dirs(path, device="cuda", write=True, lpips_weights=None, device_jp
             from .jpeg_ops import JpegWriter
             jw = JpegWriter(quality=75, subsampling="420")
         for i, (rn, gn) in enumerate(zip(rnames, gnames)):
+            if device_png:
+                break                           # (scored in groups below)
             render, gt = _load_rgb(os.path.join(rdir, rn), device), _load_rgb(os.path.join(gdir, gn), device)
             r = image_metrics(render, gt, out=table[i:i + 1], deltas=write)
             for net, lt in zip(nets, ltabs):
@@ -265,6 +296,8 @@ def evaluate_dirs(path, device="cuda", write=True, lpips_weights=None, device_jp
                 jw.submit(r.deltas.permute(0, 3, 1, 2), [os.path.join(mdir, "deltas", "{0:05d}.jpg".format(i))])
             elif write:
                 pending.append(r.deltas)
+        if device_png:
+            _score_decoded_groups(rdir, gdir, rnames, gnames, mdir, device, table, nets, ltabs, write, jw, pending, max(1, int(png_group)))
         h = table.cpu() if not nets else torch.cat([table] + [lt[:, :1] for lt in ltabs], dim=1).cpu()      # (one read either way)
         for i, d in enumerate(pending):
             Image.fromarray(d[0].cpu().numpy()).save(os.path.join(mdir, "deltas", "{0:05d}.jpg".format(i)))

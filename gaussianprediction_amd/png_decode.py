@@ -1,0 +1,319 @@
+"""PNG files decoded on the device (include/gp_png_decode.h, csrc/png_decode_kernels.hip): inflate, the Adler-32, the five row filters,
+the planar conversion with its division by 255 and, for RGBA ground truth, the composite over a background -- what the loaders did per
+file with a host library.
+
+  [REF scene/dataset_readers.py:210-218]   Image.open, convert("RGBA"), the composite in numpy
+  [REF utils/general_utils.py:21-27]       PILtoTorch: resize, / 255.0, permute
+
+The host walks the chunks (`parse`: signature, lengths, every CRC-32, IHDR) and copies the IDAT data of all files, with their segment
+tables, into ONE pinned buffer that goes up in one copy.  A file with exactly ceil(S / 16384) IDAT chunks (S = H (1 + C W)) -- every
+file png_ops writes -- is tried BANDED, one workgroup per chunk; the device proves or refutes that every chunk stands alone, and an
+image that comes back NOT_BANDED is decoded again SERIALLY, as one stream.  `decode` reads the status and mode words once per pass.
+16-bit, sub-byte, palette and interlaced files are refused on the host with a ValueError: the package has no other decoder to fall
+back to.  HIP only: CPU devices raise."""
+from __future__ import annotations
+
+import ctypes as C
+import os
+import struct
+import threading
+import zlib
+from concurrent.futures import ThreadPoolExecutor
+from types import SimpleNamespace
+
+import numpy as np
+import torch
+
+from . import _lib
+
+GP_PNG_DECODE_ABI_VERSION = 1       # include/gp_png_decode.h
+BAND_BYTES = 16384                  # GP_PNG_BAND_BYTES of include/gp_png.h: where png_ops cuts its IDAT chunks
+MAX_BATCH = 65535
+DST_U8, DST_F32 = 0, 1
+MODE_SERIAL, MODE_BANDED = 1, 2
+READER_THREADS = 4
+SIGNATURE = b"\x89PNG\r\n\x1a\n"
+CHANNELS = {0: 1, 4: 2, 2: 3, 6: 4}  # colour type -> C
+
+STATUS = {0: "OK", 1: "TRUNCATED", 2: "BLOCK_TYPE", 3: "STORED_LEN", 4: "TOO_MANY_CODES", 5: "CLEN_CODE", 6: "REPEAT_FIRST",
+          7: "REPEAT_OVERRUN", 8: "LIT_OVERSUBSCRIBED", 9: "LIT_INCOMPLETE", 10: "NO_END_OF_BLOCK", 11: "LIT_SYMBOL", 12: "DIST_SYMBOL",
+          13: "DIST_TOO_FAR", 14: "OUTPUT_LONG", 15: "OUTPUT_SHORT", 16: "ADLER", 17: "FILTER", 18: "ZLIB_METHOD", 19: "ZLIB_FDICT",
+          20: "ZLIB_FCHECK", 21: "ZLIB_WINDOW", 22: "DIST_CODE", 23: "NOT_BANDED", 24: "TRAILING", 25: "TABLE", 26: "BUDGET",
+          27: "LIT_CODE", 28: "FINAL_INSIDE"}       # GP_PNG_DECODE_* (tests/test_png_decode_host.py compares the two)
+NOT_BANDED = 23
+
+
+def _prototypes():
+    i32, i64, P = C.c_int32, C.c_int64, _lib.Ptr
+    return {   # name: (restype, argtypes), as include/gp_png_decode.h declares them (tests/test_png_decode_host.py compares the two)
+        "gp_png_decode_abi_version": (i32, []),
+        "gp_png_decode_scratch_bytes": (i64, [i32, i32, i32, i32, i32]),
+        "gp_png_decode": (i32, [i32, i32, i32, i32, i32, i32, P, i64, P, i32, P, P, P, i64, P, P, P, P]),
+    }
+
+
+PROTOTYPES = _prototypes()
+_bound = None
+_lock = threading.Lock()
+
+
+def lib() -> C.CDLL:
+    """The handle of _lib.lib() with the decoder's prototypes applied (once)."""
+    global _bound
+    if _bound is not None:
+        return _bound
+    with _lock:
+        if _bound is None:
+            l = _lib.lib()
+            rebuild = "rebuild the library (__graft_entry__.build(force=True))"
+            for name, (restype, argtypes) in PROTOTYPES.items():
+                if not hasattr(l, name):
+                    raise _lib.GpHipError(f"{_lib.LIB_PATH} does not export {name} (include/gp_png_decode.h): {rebuild}")
+                fn = getattr(l, name)
+                fn.restype, fn.argtypes = restype, argtypes
+            if int(l.gp_png_decode_abi_version()) != GP_PNG_DECODE_ABI_VERSION:
+                raise _lib.GpHipError(f"{_lib.LIB_PATH} implements PNG-decode ABI {int(l.gp_png_decode_abi_version())}, this binding is "
+                                      f"written against {GP_PNG_DECODE_ABI_VERSION} (include/gp_png_decode.h): {rebuild}")
+            _bound = l
+    return _bound
+
+
+def parse(data, name="<bytes>"):
+    """Walk the chunks of a PNG file held in `data` (bytes): the signature, every chunk's length and CRC-32, the IHDR, the IDAT chunks
+    in one run.  Returns a namespace: name, H, W, C, S = H (1 + C W), pieces (the IDAT chunks' data, views of `data`), banded (whether
+    the chunk count is the one png_ops writes, so that a banded decode is worth trying).  ValueError, naming the file and the reason,
+    for a file that is not a PNG, is damaged, or is of a kind the device decoder does not take (16-bit and sub-byte depths, palette,
+    interlace).  Nothing here touches the device."""
+    def bad(why):
+        return ValueError(f"png_decode: {name}: {why}")
+    view = memoryview(data)
+    if bytes(view[:8]) != SIGNATURE:
+        raise bad("not a PNG file (signature)")
+    pos, n, ihdr, pieces, closed, ended = 8, len(view), None, [], False, False
+    while pos < n:
+        if ended:
+            raise bad("data after IEND")
+        if pos + 12 > n:
+            raise bad("a chunk header runs past the end of the file")
+        (length,) = struct.unpack(">I", view[pos:pos + 4])
+        kind = bytes(view[pos + 4:pos + 8])
+        if length > n - pos - 12:
+            raise bad(f"chunk {kind!r} of {length} bytes runs past the end of the file")
+        body = view[pos + 8:pos + 8 + length]
+        (crc,) = struct.unpack(">I", view[pos + 8 + length:pos + 12 + length])
+        if crc != zlib.crc32(view[pos + 4:pos + 8 + length]):
+            raise bad(f"CRC-32 of chunk {kind!r} at byte {pos}")
+        if ihdr is None and kind != b"IHDR":
+            raise bad("the first chunk is not IHDR")
+        if kind == b"IHDR":
+            if ihdr is not None or length != 13:
+                raise bad("IHDR")
+            ihdr = struct.unpack(">IIBBBBB", body)
+        elif kind == b"IDAT":
+            if closed:
+                raise bad("IDAT chunks are not consecutive")
+            pieces.append(body)
+        else:
+            closed = closed or bool(pieces)
+            ended = kind == b"IEND"
+        pos += 12 + length
+    if ihdr is None:
+        raise bad("no IHDR")
+    if not ended:
+        raise bad("no IEND")
+    W, H, depth, colour, comp, filt, lace = ihdr
+    if W < 1 or H < 1 or comp != 0 or filt != 0 or lace not in (0, 1):
+        raise bad(f"IHDR: {W} x {H}, compression {comp}, filter {filt}, interlace {lace}")
+    if colour == 3:
+        raise bad("palette images are not decoded on the device")
+    if colour not in CHANNELS or depth not in (1, 2, 4, 8, 16):
+        raise bad(f"IHDR: colour type {colour}, bit depth {depth}")
+    if depth != 8:
+        raise bad(f"bit depth {depth}: only 8-bit samples are decoded on the device")
+    if lace:
+        raise bad("interlaced images are not decoded on the device")
+    if not pieces:
+        raise bad("no IDAT chunk")
+    Cn = CHANNELS[colour]
+    S = H * (1 + Cn * W)
+    if S >= 1 << 31 or H > 65535:
+        raise bad(f"{W} x {H} x {Cn}: beyond the limits of include/gp_png_decode.h")
+    return SimpleNamespace(name=name, H=H, W=W, C=Cn, S=S, pieces=pieces, banded=len(pieces) > 1 and len(pieces) == -(-S // BAND_BYTES))
+
+
+def _device(device):
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"png_decode: device {device} -- HIP kernels only (no CPU fallback)")
+    return torch.device("cuda", torch.cuda.current_device()) if device.index is None else device
+
+
+def _arguments(device, dtype, background):
+    device = _device(device)
+    if dtype not in (torch.uint8, torch.float32):
+        raise RuntimeError(f"png_decode: dtype must be torch.uint8 or torch.float32 (got {dtype})")
+    if background is not None:
+        if not torch.is_tensor(background) or background.numel() != 3 or not background.dtype.is_floating_point:
+            raise RuntimeError("png_decode: background must be a tensor of three floats")
+        if not background.is_cuda:
+            raise RuntimeError(f"png_decode: background is on {background.device} -- HIP kernels only (no CPU fallback)")
+        background = background.detach().to(device=device, dtype=torch.float32).reshape(3).contiguous()
+    return device, background
+
+
+def groups(items, channels=None, background=None):
+    """The images by shape, in order of first appearance: [((H, W, C), C_out, [index])].  Checked before the device."""
+    by_shape = {}
+    for i, it in enumerate(items):
+        by_shape.setdefault((it.H, it.W, it.C), []).append(i)
+    out = []
+    for (H, W, Cn), idx in by_shape.items():
+        if background is not None and Cn != 4:
+            raise ValueError(f"png_decode: {items[idx[0]].name}: a background composites RGBA images, this one has {Cn} channel(s)")
+        c_out = 3 if background is not None and channels is None else Cn if channels is None else min(int(channels), Cn)
+        if c_out < 1 or (background is not None and c_out != 3):
+            raise ValueError(f"png_decode: {items[idx[0]].name}: channels = {c_out} of an image with {Cn}" + (" and a background" if background is not None else ""))
+        for lo in range(0, len(idx), MAX_BATCH):
+            out.append(((H, W, Cn), c_out, idx[lo:lo + MAX_BATCH]))
+    return out
+
+
+def tables(items, banded, idx):
+    """The tables of one shape group (the images idx of items) as include/gp_png_decode.h states them: (segments [(image, first payload
+    byte, the byte after the last, out_first, out_len)], image_seg [B + 1], copies [(payload offset, piece)], payload bytes).  A banded
+    image has one segment per IDAT chunk, writing GP_PNG_BAND_BYTES of the filtered stream each; a serial one is one segment."""
+    seg, image_seg, at, copies = [], [0], 0, []
+    for b, i in enumerate(idx):
+        it = items[i]
+        first = at
+        for k, piece in enumerate(it.pieces):
+            if banded[i]:
+                seg.append((b, at, at + len(piece), k * BAND_BYTES, min(BAND_BYTES, it.S - k * BAND_BYTES)))
+            copies.append((at, piece))
+            at += len(piece)
+        if not banded[i]:
+            seg.append((b, first, at, 0, it.S))
+        image_seg.append(len(seg))
+    return seg, image_seg, copies, at
+
+
+def stage(items, banded, shapes, pool=None):
+    """The pinned staging buffer of one pass: all segment tables (int64), all image tables (int32), then every group's joined IDAT
+    data with the chunk framing gone.  Returns a namespace: buffer, plans (per group: seg, image_seg, bytes and where its parts lie)."""
+    plans, nseg_all, nimg_all, pay_all = [], 0, 0, 0
+    for _, _, idx in shapes:
+        seg, image_seg, copies, at = tables(items, banded, idx)
+        plans.append(SimpleNamespace(seg=seg, image_seg=image_seg, bytes=at, copies=copies, seg_at=nseg_all * 40, pay_at=pay_all))
+        nseg_all += len(seg)
+        nimg_all += len(image_seg)
+        pay_all += -(-at // 16) * 16
+    img_off = nseg_all * 40
+    pay_off = -(-(img_off + 4 * nimg_all) // 256) * 256
+    for pl in plans:
+        pl.img_at, img_off = img_off, img_off + 4 * len(pl.image_seg)
+        pl.pay_at += pay_off
+    staging = torch.empty(pay_off + pay_all + 16, dtype=torch.uint8, pin_memory=True)
+    host = staging.numpy()
+    host[:nseg_all * 40].view(np.int64)[:] = np.array([s for pl in plans for s in pl.seg], dtype=np.int64).reshape(-1)
+    host[nseg_all * 40:img_off].view(np.int32)[:] = np.array([v for pl in plans for v in pl.image_seg], dtype=np.int32)
+
+    def copy(job):
+        at, piece = job
+        host[at:at + len(piece)] = np.frombuffer(piece, dtype=np.uint8)
+
+    jobs = [(pl.pay_at + at, piece) for pl in plans for at, piece in pl.copies]
+    if pool is not None and len(jobs) > 1:
+        list(pool.map(copy, jobs, chunksize=max(1, len(jobs) // (4 * READER_THREADS))))
+    else:
+        for job in jobs:
+            copy(job)
+    return SimpleNamespace(buffer=staging, plans=plans)
+
+
+def launch(staged, up, shapes, words, *, device, dtype, background, guard=0):
+    """One gp_png_decode call per shape group on `up`, the staging buffer's copy on the device; words: int32 [2, images] on the device
+    for the status and mode words, in group order.  Nothing is read.  Returns (per group the [B, C_out H W + guard] output buffer)."""
+    l, slots, done = lib(), [], 0
+    with _lib.on_device(device):
+        for ((H, W, Cn), c_out, idx), pl in zip(shapes, staged.plans):
+            B, stride = len(idx), c_out * H * W + int(guard)
+            n = int(l.gp_png_decode_scratch_bytes(B, H, W, Cn, len(pl.seg)))
+            if n < 0:
+                raise _lib.GpHipError(f"gp_png_decode_scratch_bytes: {l.gp_last_error().decode(errors='replace')}")
+            scratch = torch.empty(n, dtype=torch.uint8, device=device)          # (the caching allocator aligns to 512 bytes)
+            dst = torch.empty(B, stride, dtype=dtype, device=device)
+            if guard:
+                dst.view(torch.uint8).fill_(0xA5)
+            _lib.check(l.gp_png_decode(B, H, W, Cn, c_out, DST_U8 if dtype == torch.uint8 else DST_F32, up[pl.pay_at:], pl.bytes,
+                                       up[pl.seg_at:], len(pl.seg), up[pl.img_at:], background, dst, stride, words[0, done:], words[1, done:],
+                                       scratch, _lib.stream_ptr(device)), "gp_png_decode")
+            slots.append(dst)
+            done += B
+    return slots
+
+
+def decode_once(items, banded, *, device, dtype=torch.uint8, channels=None, background=None, guard=0, pool=None):
+    """One pass over parsed files (`parse`), image i banded where banded[i]: one pinned staging buffer, one copy up, one gp_png_decode
+    call per shape group, ONE read of the status and mode words.  Returns (images: a list of [C_out, H, W] device tensors, views of
+    their group's batch; status and modes: lists of ints; slots: per group the whole [B, C_out H W + guard] buffer, whose `guard`
+    trailing elements per image were filled with 0xA5 bytes before the call -- the tests look at them)."""
+    device, background = _arguments(device, dtype, background)
+    if not items:
+        return [], [], [], []
+    shapes = groups(items, channels, background)
+    staged = stage(items, banded, shapes, pool)
+    with _lib.on_device(device):
+        up = staged.buffer.to(device, non_blocking=True)                        # the one copy
+        words = torch.empty(2, len(items), dtype=torch.int32, device=device)
+        slots = launch(staged, up, shapes, words, device=device, dtype=dtype, background=background, guard=guard)
+        read = words.cpu().tolist()                                             # the one read (it also ends the staging buffer's use)
+    images, status, modes, k = [None] * len(items), [0] * len(items), [0] * len(items), 0
+    for ((H, W, Cn), c_out, idx), dst in zip(shapes, slots):
+        for b, i in enumerate(idx):
+            images[i] = dst[b, :c_out * H * W].view(c_out, H, W)
+            status[i], modes[i] = read[0][k], read[1][k]
+            k += 1
+    return images, status, modes, slots
+
+
+def decode(files, *, device, dtype=torch.uint8, channels=None, background=None, names=None, return_modes=False, _pool=None):
+    """PNG files held in memory (a list of bytes) -> a list of [C_out, H, W] tensors on `device`, one per file, in order.
+    dtype: torch.uint8, or torch.float32 = byte / 255 (bit-equal to uint8.to(float32) / 255.0).  channels: keep the first `channels`
+    channels, as the slice [:channels] would (default: all).  background: three floats on the device -- RGBA files are composited over it to three channels as the
+    D-NeRF reader does [REF scene/dataset_readers.py:212-218].  The files are grouped by shape; a group is one launch sequence.  The
+    device is read once, and once more only if a file that looked banded was not (those are decoded again as one stream).  A
+    damaged file raises GpHipError naming the file and the status word.  return_modes: also the final mode per file
+    (MODE_BANDED / MODE_SERIAL)."""
+    _arguments(device, dtype, background)                                       # (the device is checked before any file is looked at)
+    files = list(files)
+    names = [f"<file {i}>" for i in range(len(files))] if names is None else [os.fspath(n) for n in names]
+    if len(names) != len(files):
+        raise RuntimeError(f"png_decode: {len(files)} files but {len(names)} names")
+    items = [f if isinstance(f, SimpleNamespace) else parse(f, n) for f, n in zip(files, names)]
+    kw = dict(device=device, dtype=dtype, channels=channels, background=background, pool=_pool)
+    banded = [it.banded for it in items]
+    images, status, modes, _ = decode_once(items, banded, **kw)
+    again = [i for i, s in enumerate(status) if s == NOT_BANDED and banded[i]]
+    if again:
+        im2, st2, mo2, _ = decode_once([items[i] for i in again], [False] * len(again), **kw)
+        for k, i in enumerate(again):
+            images[i], status[i], modes[i] = im2[k], st2[k], mo2[k]
+    for it, s in zip(items, status):
+        if s:
+            raise _lib.GpHipError(f"png_decode: {it.name}: the device decoder reports status {s} (GP_PNG_DECODE_{STATUS.get(s, '?')})")
+    return (images, modes) if return_modes else images
+
+
+def decode_files(paths, *, device, dtype=torch.uint8, channels=None, background=None, return_modes=False):
+    """`decode` of files on disk: at most READER_THREADS threads read and parse them and fill the staging buffer."""
+    _arguments(device, dtype, background)
+    paths = [os.fspath(p) for p in paths]
+
+    def load(path):
+        with open(path, "rb") as fp:
+            return parse(fp.read(), path)
+
+    with ThreadPoolExecutor(max_workers=max(1, min(READER_THREADS, len(paths)))) as pool:
+        items = list(pool.map(load, paths))
+        return decode(items, device=device, dtype=dtype, channels=channels, background=background, names=paths,
+                      return_modes=return_modes, _pool=pool)
