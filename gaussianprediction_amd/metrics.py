@@ -225,14 +225,45 @@ def _lpips_from(weights, device):
     return [_lp.cached(net, device, os.fspath(weights)) for net in ("vgg", "alex")]
 
 
-def _score_decoded_groups(rdir, gdir, rnames, gnames, mdir, device, table, nets, ltabs, write, jw, pending, group):
+def _decode_by_signature(paths, device):
+    """evaluate_dirs' device_decode: every file goes by its first bytes to png_decode or jpeg_decode (float32, the first three
+    channels); one call of each per group.  Anything else raises, naming the file: there is no host decoder behind this path."""
+    from . import jpeg_decode, png_decode
+    kinds = {"png": ([], []), "jpeg": ([], [])}
+    for i, path in enumerate(paths):
+        with open(path, "rb") as fp:
+            data = fp.read()
+        if data[:8] == png_decode.SIGNATURE:
+            kind = "png"
+        elif data[:2] == b"\xff\xd8":
+            kind = "jpeg"
+        else:
+            raise RuntimeError(f"evaluate_dirs: {path} is neither a PNG nor a JPEG file (device_decode reads these two)")
+        kinds[kind][0].append(i)
+        kinds[kind][1].append(data)
+    out = [None] * len(paths)
+    for kind, (idx, files) in kinds.items():
+        if not files:
+            continue
+        names = [paths[i] for i in idx]
+        if kind == "png":
+            imgs = png_decode.decode(files, device=device, dtype=torch.float32, channels=3, names=names)
+        else:
+            imgs = jpeg_decode.decode(files, device=device, dtype=torch.float32, names=names)
+        for i, im in zip(idx, imgs):
+            out[i] = im
+    return out
+
+
+def _score_decoded_groups(rdir, gdir, rnames, gnames, mdir, device, table, nets, ltabs, write, jw, pending, group, by_signature=False):
     """evaluate_dirs' loop with device_png: `group` pairs per png_decode.decode_files call (float32, the first three channels), and
-    one batched image_metrics call per run of pairs of one shape."""
+    one batched image_metrics call per run of pairs of one shape.  by_signature (device_decode): PNG and JPEG files, each to its
+    decoder."""
     from . import png_decode
     for lo in range(0, len(rnames), group):
         hi = min(len(rnames), lo + group)
-        imgs = png_decode.decode_files([os.path.join(rdir, n) for n in rnames[lo:hi]] + [os.path.join(gdir, n) for n in gnames[lo:hi]],
-                                       device=device, dtype=torch.float32, channels=3)
+        paths = [os.path.join(rdir, n) for n in rnames[lo:hi]] + [os.path.join(gdir, n) for n in gnames[lo:hi]]
+        imgs = _decode_by_signature(paths, device) if by_signature else png_decode.decode_files(paths, device=device, dtype=torch.float32, channels=3)
         renders, gts = imgs[:hi - lo], imgs[hi - lo:]
         i = lo
         while i < hi:
@@ -251,7 +282,7 @@ def _score_decoded_groups(rdir, gdir, rnames, gnames, mdir, device, table, nets,
             i = j
 
 
-def evaluate_dirs(path, device="cuda", write=True, lpips_weights=None, device_jpeg=False, device_png=False, png_group=16):
+def evaluate_dirs(path, device="cuda", write=True, lpips_weights=None, device_jpeg=False, device_png=False, png_group=16, device_decode=False):
     """The directory form of the reference's metrics.py [REF metrics.py:113-178]: for every `<path>/<method>/` holding `renders/`
     and `gt/`, score the sorted image pairs (files whose name contains "depth" are skipped), write `<method>/deltas/%05d.jpg` and
     -- as the reference does -- `<path>/results.json` and `<path>/per_view.json` of the last method.  Keys: SSIM, PSNR, MS-SSIM,
@@ -262,6 +293,8 @@ def evaluate_dirs(path, device="cuda", write=True, lpips_weights=None, device_jp
     device_png: the image pairs are decoded on the device (png_decode.decode_files: float32, the first three channels), `png_group`
     pairs per call, and every run of equal-shaped pairs of a group is scored by one batched image_metrics call, instead of one host
     decode per file; the numbers are the same.
+    device_decode: as device_png, but every file goes by its signature to png_decode or to jpeg_decode (baseline JPEG, 4:4:4 or
+    4:2:0) -- a gt directory of .jpg frames, or .jpg renders; the numbers are the default path's.  Off by default.
     Returns {method: {"summary": ..., "per_view": ...}} with the dictionaries that were written."""
     from PIL import Image
     device = torch.device(device)
@@ -286,7 +319,7 @@ def evaluate_dirs(path, device="cuda", write=True, lpips_weights=None, device_jp
             from .jpeg_ops import JpegWriter
             jw = JpegWriter(quality=75, subsampling="420")
         for i, (rn, gn) in enumerate(zip(rnames, gnames)):
-            if device_png:
+            if device_png or device_decode:
                 break                           # (scored in groups below)
             render, gt = _load_rgb(os.path.join(rdir, rn), device), _load_rgb(os.path.join(gdir, gn), device)
             r = image_metrics(render, gt, out=table[i:i + 1], deltas=write)
@@ -296,8 +329,9 @@ def evaluate_dirs(path, device="cuda", write=True, lpips_weights=None, device_jp
                 jw.submit(r.deltas.permute(0, 3, 1, 2), [os.path.join(mdir, "deltas", "{0:05d}.jpg".format(i))])
             elif write:
                 pending.append(r.deltas)
-        if device_png:
-            _score_decoded_groups(rdir, gdir, rnames, gnames, mdir, device, table, nets, ltabs, write, jw, pending, max(1, int(png_group)))
+        if device_png or device_decode:
+            _score_decoded_groups(rdir, gdir, rnames, gnames, mdir, device, table, nets, ltabs, write, jw, pending, max(1, int(png_group)),
+                                  by_signature=bool(device_decode))
         h = table.cpu() if not nets else torch.cat([table] + [lt[:, :1] for lt in ltabs], dim=1).cpu()      # (one read either way)
         for i, d in enumerate(pending):
             Image.fromarray(d[0].cpu().numpy()).save(os.path.join(mdir, "deltas", "{0:05d}.jpg".format(i)))
