@@ -8,7 +8,8 @@ division by 255 -- what the loaders did per file with a host library -- and the 
 
 The host walks the markers (`parse`), finds the restart intervals by their RST markers and copies the scans of all files, with
 their segment tables and their quantisation and Huffman tables, into ONE pinned buffer that goes up in one copy.  Every
-file jpeg_ops writes carries a restart marker every 8 MCUs; a file without restart markers is one interval, one lane, and slow.
+file jpeg_ops writes carries a restart marker every 8 MCUs; a file without restart markers is one interval, one lane, and slow --
+unless `sync` sends it through jpeg_sync, which decodes it on many lanes.
 `decode` reads the status words once.  Progressive, extended, arithmetic-coded, 12-bit, greyscale, CMYK, 4:2:2 / 4:4:0 / 4:1:1 and
 multi-scan files are refused on the host with a ValueError: the package has no other decoder to fall back to.  HIP only: CPU
 devices raise."""
@@ -377,27 +378,48 @@ def decode_once(items, *, device, dtype=torch.uint8, guard=0, pool=None):
     return images, status, slots
 
 
-def decode(files, *, device, dtype=torch.uint8, names=None, _pool=None):
+def _sync_flag(sync):
+    if sync is not False and sync is not True and sync != "auto":
+        raise RuntimeError(f"jpeg_decode: sync must be False, True or \"auto\" (got {sync!r})")
+    return bool(sync)
+
+
+def decode(files, *, device, dtype=torch.uint8, names=None, sync=False, _pool=None):
     """JPEG files held in memory (a list of bytes) -> a list of [3, H, W] R G B tensors on `device`, one per file, in order.
     dtype: torch.uint8, or torch.float32 = byte / 255 (bit-equal to uint8.to(float32) / 255.0).  The files are grouped by shape and
     subsampling; a group is one launch sequence.  The device is read once.  A damaged file raises GpHipError naming the file and the
-    status word."""
+    status word.
+    sync: True or "auto" sends the files without restart markers that jpeg_sync.eligible takes through jpeg_sync.decode_once (many
+    lanes per file instead of one); what comes back SERIAL there, and every other file, goes through the one-lane call in a second
+    pass, so the pixels and every error are those of sync=False.  Off by default."""
     _arguments(device, dtype)                                                   # (the device is checked before any file is looked at)
+    sync = _sync_flag(sync)
     files = list(files)
     names = [f"<file {i}>" for i in range(len(files))] if names is None else [os.fspath(n) for n in names]
     if len(names) != len(files):
         raise RuntimeError(f"jpeg_decode: {len(files)} files but {len(names)} names")
     items = [f if isinstance(f, SimpleNamespace) else parse(f, n) for f, n in zip(files, names)]
-    images, status, _ = decode_once(items, device=device, dtype=dtype, pool=_pool)
-    for it, s in zip(items, status):
+    images, rest = [None] * len(items), list(range(len(items)))
+    if sync:
+        from . import jpeg_sync
+        fast = [i for i in rest if jpeg_sync.eligible(items[i])]
+        got, words, _ = jpeg_sync.decode_once([items[i] for i in fast], device=device, dtype=dtype, pool=_pool)
+        for i, im, s in zip(fast, got, words):
+            if s == jpeg_sync.OK:
+                images[i] = im
+        rest = [i for i in rest if images[i] is None]
+    got, status, _ = decode_once([items[i] for i in rest], device=device, dtype=dtype, pool=_pool)
+    for i, im, s in zip(rest, got, status):
         if s:
-            raise _lib.GpHipError(f"jpeg_decode: {it.name}: the device decoder reports status {s} (GP_JPEG_DECODE_{STATUS.get(s, '?')})")
+            raise _lib.GpHipError(f"jpeg_decode: {items[i].name}: the device decoder reports status {s} (GP_JPEG_DECODE_{STATUS.get(s, '?')})")
+        images[i] = im
     return images
 
 
-def decode_files(paths, *, device, dtype=torch.uint8):
+def decode_files(paths, *, device, dtype=torch.uint8, sync=False):
     """`decode` of files on disk: at most READER_THREADS threads read and parse them and fill the staging buffer."""
     _arguments(device, dtype)
+    _sync_flag(sync)
     paths = [os.fspath(p) for p in paths]
 
     def load(path):
@@ -406,7 +428,7 @@ def decode_files(paths, *, device, dtype=torch.uint8):
 
     with ThreadPoolExecutor(max_workers=max(1, min(READER_THREADS, len(paths)))) as pool:
         items = list(pool.map(load, paths))
-        return decode(items, device=device, dtype=dtype, names=paths, _pool=pool)
+        return decode(items, device=device, dtype=dtype, names=paths, sync=sync, _pool=pool)
 
 
 # ---- Motion-JPEG in AVI ----------------------------------------------------------------------------------------------------------------
@@ -466,10 +488,12 @@ def avi_frames(data, name="<bytes>"):
     return width, abs(height), found["frames"]
 
 
-def decode_avi(path, *, device, dtype=torch.uint8, frames=None):
+def decode_avi(path, *, device, dtype=torch.uint8, frames=None, sync=False):
     """The frames of a Motion-JPEG AVI file (one MJPG video stream, as jpeg_ops.VideoWriter writes it) as one [F, 3, H, W] tensor on
-    `device`.  frames: the frame numbers to decode, in the order wanted (default: all).  AVI_BATCH frames per decode call."""
+    `device`.  frames: the frame numbers to decode, in the order wanted (default: all).  AVI_BATCH frames per decode call.  sync: as
+    `decode` -- the frames other encoders write carry no restart markers."""
     device = _arguments(device, dtype)
+    _sync_flag(sync)
     path = os.fspath(path)
     with open(path, "rb") as fp:
         data = fp.read()
@@ -484,6 +508,6 @@ def decode_avi(path, *, device, dtype=torch.uint8, frames=None):
             raise ValueError(f"jpeg_decode: {it.name}: a frame of {it.H} x {it.W} in a video of {height} x {width}")
     out = torch.empty(len(items), 3, height, width, dtype=dtype, device=device)
     for lo in range(0, len(items), AVI_BATCH):
-        imgs = decode(items[lo:lo + AVI_BATCH], device=device, dtype=dtype)
+        imgs = decode(items[lo:lo + AVI_BATCH], device=device, dtype=dtype, sync=sync)
         out[lo:lo + len(imgs)] = torch.stack(imgs)
     return out

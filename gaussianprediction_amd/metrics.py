@@ -225,7 +225,7 @@ def _lpips_from(weights, device):
     return [_lp.cached(net, device, os.fspath(weights)) for net in ("vgg", "alex")]
 
 
-def _decode_by_signature(paths, device):
+def _decode_by_signature(paths, device, sync=False):
     """evaluate_dirs' device_decode: every file goes by its first bytes to png_decode or jpeg_decode (float32, the first three
     channels); one call of each per group.  Anything else raises, naming the file: there is no host decoder behind this path."""
     from . import jpeg_decode, png_decode
@@ -249,13 +249,13 @@ def _decode_by_signature(paths, device):
         if kind == "png":
             imgs = png_decode.decode(files, device=device, dtype=torch.float32, channels=3, names=names)
         else:
-            imgs = jpeg_decode.decode(files, device=device, dtype=torch.float32, names=names)
+            imgs = jpeg_decode.decode(files, device=device, dtype=torch.float32, names=names, sync=sync)
         for i, im in zip(idx, imgs):
             out[i] = im
     return out
 
 
-def _score_decoded_groups(rdir, gdir, rnames, gnames, mdir, device, table, nets, ltabs, write, jw, pending, group, by_signature=False):
+def _score_decoded_groups(rdir, gdir, rnames, gnames, mdir, device, table, nets, ltabs, write, jw, pending, group, by_signature=False, sync=False):
     """evaluate_dirs' loop with device_png: `group` pairs per png_decode.decode_files call (float32, the first three channels), and
     one batched image_metrics call per run of pairs of one shape.  by_signature (device_decode): PNG and JPEG files, each to its
     decoder."""
@@ -263,7 +263,7 @@ def _score_decoded_groups(rdir, gdir, rnames, gnames, mdir, device, table, nets,
     for lo in range(0, len(rnames), group):
         hi = min(len(rnames), lo + group)
         paths = [os.path.join(rdir, n) for n in rnames[lo:hi]] + [os.path.join(gdir, n) for n in gnames[lo:hi]]
-        imgs = _decode_by_signature(paths, device) if by_signature else png_decode.decode_files(paths, device=device, dtype=torch.float32, channels=3)
+        imgs = _decode_by_signature(paths, device, sync) if by_signature else png_decode.decode_files(paths, device=device, dtype=torch.float32, channels=3)
         renders, gts = imgs[:hi - lo], imgs[hi - lo:]
         i = lo
         while i < hi:
@@ -282,7 +282,7 @@ def _score_decoded_groups(rdir, gdir, rnames, gnames, mdir, device, table, nets,
             i = j
 
 
-def evaluate_dirs(path, device="cuda", write=True, lpips_weights=None, device_jpeg=False, device_png=False, png_group=16, device_decode=False):
+def evaluate_dirs(path, device="cuda", write=True, lpips_weights=None, device_jpeg=False, device_png=False, png_group=16, device_decode=False, decode_sync=False):
     """The directory form of the reference's metrics.py [REF metrics.py:113-178]: for every `<path>/<method>/` holding `renders/`
     and `gt/`, score the sorted image pairs (files whose name contains "depth" are skipped), write `<method>/deltas/%05d.jpg` and
     -- as the reference does -- `<path>/results.json` and `<path>/per_view.json` of the last method.  Keys: SSIM, PSNR, MS-SSIM,
@@ -295,6 +295,8 @@ def evaluate_dirs(path, device="cuda", write=True, lpips_weights=None, device_jp
     decode per file; the numbers are the same.
     device_decode: as device_png, but every file goes by its signature to png_decode or to jpeg_decode (baseline JPEG, 4:4:4 or
     4:2:0) -- a gt directory of .jpg frames, or .jpg renders; the numbers are the default path's.  Off by default.
+    decode_sync: with device_decode, jpeg_decode.decode's `sync` -- JPEG files without restart markers go through jpeg_sync's many
+    lanes; the pixels, and so the numbers, are the same.  Off by default.
     Returns {method: {"summary": ..., "per_view": ...}} with the dictionaries that were written."""
     from PIL import Image
     device = torch.device(device)
@@ -331,7 +333,7 @@ def evaluate_dirs(path, device="cuda", write=True, lpips_weights=None, device_jp
                 pending.append(r.deltas)
         if device_png or device_decode:
             _score_decoded_groups(rdir, gdir, rnames, gnames, mdir, device, table, nets, ltabs, write, jw, pending, max(1, int(png_group)),
-                                  by_signature=bool(device_decode))
+                                  by_signature=bool(device_decode), sync=decode_sync)
         h = table.cpu() if not nets else torch.cat([table] + [lt[:, :1] for lt in ltabs], dim=1).cpu()      # (one read either way)
         for i, d in enumerate(pending):
             Image.fromarray(d[0].cpu().numpy()).save(os.path.join(mdir, "deltas", "{0:05d}.jpg".format(i)))
