@@ -712,6 +712,8 @@ __global__ __launch_bounds__(256) void gp_hashgrid_bwd_slots_kernel(HashGridDev 
                     }
                 }
                 __syncthreads();
+            } else {
+                __syncthreads();   // every wave holds the bounds in registers before the next dense level resets s_lo / s_hi
             }
         }
         if (!boxed && live) {
