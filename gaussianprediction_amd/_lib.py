@@ -1,4 +1,4 @@
-"""ctypes binding of libgp_hip.so (C ABI declared in include/gp_hip.h).
+"""ctypes binding of libgp_hip.so: the C ABI of include/gp_hip.h, and the one loop (Abi) that binds every header of include/.
 
 The HIP library is the product; there is NO CPU or eager-PyTorch fallback.  If the shared library is
 missing or cannot be loaded this module raises immediately and loudly.
@@ -218,16 +218,51 @@ def _prototypes():
     }
 
 
+class GpHipError(RuntimeError):
+    pass
+
+
+_lib = None                # the CDLL, once the main table is applied: lib()'s fast path reads nothing else
+_lock = threading.RLock()
+ABIS = []                  # every Abi, in import order; the main one (include/gp_hip.h) first
+
+
+class Abi:
+    """One header of include/ and its binding: the header's file name, the name of its *_abi_version function, the version this
+    binding is written against, and {name: (restype, argtypes)} as the header declares them (tests/abi_check.py compares the two).
+    Constructing one registers it in ABIS; lib() applies the table to the one CDLL handle and checks the version, once."""
+
+    def __init__(self, header, version_fn, version, prototypes):
+        self.header, self.version_fn, self.version, self.prototypes = header, version_fn, version, prototypes
+        self._handle = None
+        ABIS.append(self)
+
+    def bind(self, l):
+        rebuild = "rebuild the library (__graft_entry__.build(force=True))"
+        for name, (restype, argtypes) in self.prototypes.items():
+            if not hasattr(l, name):
+                raise GpHipError(f"{LIB_PATH} does not export {name} (include/{self.header}): {rebuild}")
+            fn = getattr(l, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        got = int(getattr(l, self.version_fn)())
+        if got != self.version:
+            raise GpHipError(f"{LIB_PATH} implements {self.header} ABI {got}, this binding is written against {self.version}: {rebuild}")
+        return l
+
+    def lib(self) -> C.CDLL:
+        """The handle of _lib.lib() with this table applied (once)."""
+        if self._handle is None:
+            with _lock:
+                l = lib()                                   # (binds the main ABI, if this is the first call of all)
+                if self._handle is None:
+                    self._handle = self.bind(l)
+        return self._handle
+
+
 PROTOTYPES = _prototypes()
 EXPORTS = list(PROTOTYPES)
 GP_ABI_VERSION = 9         # include/gp_hip.h: the struct layouts / signatures / buffer-size macros this binding was written against
-
-_lib = None
-_lock = threading.Lock()
-
-
-class GpHipError(RuntimeError):
-    pass
+ABI = Abi("gp_hip.h", "gp_abi_version", GP_ABI_VERSION, PROTOTYPES)
 
 
 def lib() -> C.CDLL:
@@ -236,29 +271,33 @@ def lib() -> C.CDLL:
     if _lib is not None:
         return _lib
     with _lock:
-        if _lib is not None:
-            return _lib
-        if not os.path.exists(LIB_PATH):
-            raise GpHipError(
-                f"{LIB_PATH} not found: the HIP extension is the only implementation of this path (no CPU/eager "
-                "fallback). Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                "(hipcc --offload-arch=gfx950).")
-        l = C.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in PROTOTYPES.items():
-            if not hasattr(l, name):
-                raise GpHipError(f"{LIB_PATH} does not export {name}")
-            fn = getattr(l, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        if int(l.gp_abi_version()) != GP_ABI_VERSION:
-            raise GpHipError(f"{LIB_PATH} implements ABI {int(l.gp_abi_version())}, this binding is written against ABI "
-                             f"{GP_ABI_VERSION} (include/gp_hip.h): rebuild the library (__graft_entry__.build(force=True))")
-        _lib = l
-        return _lib
+        if _lib is None:
+            if not os.path.exists(LIB_PATH):
+                raise GpHipError(
+                    f"{LIB_PATH} not found: the HIP extension is the only implementation of this path (no CPU/eager "
+                    "fallback). Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                    "(hipcc --offload-arch=gfx950).")
+            _lib = ABI._handle = ABI.bind(C.CDLL(LIB_PATH))
+    return _lib
+
+
+def last_error() -> str:
+    """The library's message for the call that failed last."""
+    return lib().gp_last_error().decode(errors="replace")
 
 
 def check(rc: int, what: str) -> None:
     if rc != 0:
-        raise GpHipError(f"{what}: {lib().gp_last_error().decode(errors='replace')}")
+        raise GpHipError(f"{what}: {last_error()}")
+
+
+def scratch(query, *args, device, extra=0):
+    """The uint8 buffer on `device` of query(*args) + extra bytes, query being a bound gp_*_scratch_bytes entry point (a negative
+    answer is the library's refusal of the arguments)."""
+    n = int(query(*args))
+    if n < 0:
+        raise GpHipError(f"{query.__name__}: {last_error()}")
+    return torch.empty(n + extra, dtype=torch.uint8, device=device)          # (the caching allocator aligns to 512 bytes)
 
 
 def ptr(t):

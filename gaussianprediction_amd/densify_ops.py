@@ -9,7 +9,6 @@ Nothing here reads the device; the caller reads the status block when it needs t
 from __future__ import annotations
 
 import ctypes as C
-import threading
 
 import torch
 
@@ -45,29 +44,8 @@ def _prototypes():
 
 
 PROTOTYPES = _prototypes()
-_bound = None
-_lock = threading.Lock()
-
-
-def lib() -> C.CDLL:
-    """The handle of _lib.lib() with the densify prototypes applied (once)."""
-    global _bound
-    if _bound is not None:
-        return _bound
-    with _lock:
-        if _bound is None:
-            l = _lib.lib()
-            rebuild = "rebuild the library (__graft_entry__.build(force=True))"
-            for name, (restype, argtypes) in PROTOTYPES.items():
-                if not hasattr(l, name):
-                    raise _lib.GpHipError(f"{_lib.LIB_PATH} does not export {name} (include/gp_densify.h): {rebuild}")
-                fn = getattr(l, name)
-                fn.restype, fn.argtypes = restype, argtypes
-            if int(l.gp_densify_abi_version()) != GP_DENSIFY_ABI_VERSION:
-                raise _lib.GpHipError(f"{_lib.LIB_PATH} implements densify ABI {int(l.gp_densify_abi_version())}, this binding is written "
-                                      f"against {GP_DENSIFY_ABI_VERSION} (include/gp_densify.h): {rebuild}")
-            _bound = l
-    return _bound
+ABI = _lib.Abi("gp_densify.h", "gp_densify_abi_version", GP_DENSIFY_ABI_VERSION, PROTOTYPES)
+lib = ABI.lib            # the handle of _lib.lib() with this table applied (once)
 
 
 def _device_f32(t, name, shape=None, dtype=torch.float32):
@@ -113,10 +91,7 @@ def plan(accum, denom, max_radii2D, scaling, opacity, grad_threshold, dense_exte
     for name, t, k in (("accum", accum, 1), ("denom", denom, 1), ("max_radii2D", max_radii2D, 1), ("scaling", scaling, 3), ("opacity", opacity, 1)):
         _device_f32(t, name, k * n)
     dev, l = opacity.device, lib()
-    nbytes = int(l.gp_densify_scratch_bytes(n))
-    if nbytes < 0:
-        raise _lib.GpHipError(f"gp_densify_scratch_bytes: {l.gp_last_error().decode(errors='replace')}")
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)          # (the caching allocator aligns to 512 bytes)
+    scratch = _lib.scratch(l.gp_densify_scratch_bytes, n, device=dev)
     status = torch.empty(STATUS_WORDS, dtype=torch.int32, device=dev)
     flags = flags_of(do_densify, do_reset, do_prune, max_screen_size)
     with _lib.on_device(dev):

@@ -9,7 +9,6 @@ No kernel uses a float atomic: two calls on equal inputs give equal bits.  Nothi
 from __future__ import annotations
 
 import ctypes as C
-import threading
 
 import torch
 
@@ -35,29 +34,8 @@ def _prototypes():
 
 
 PROTOTYPES = _prototypes()
-_bound = None
-_lock = threading.Lock()
-
-
-def lib() -> C.CDLL:
-    """The handle of _lib.lib() with the GCN prototypes applied (once)."""
-    global _bound
-    if _bound is not None:
-        return _bound
-    with _lock:
-        if _bound is None:
-            l = _lib.lib()
-            rebuild = "rebuild the library (__graft_entry__.build(force=True))"
-            for name, (restype, argtypes) in PROTOTYPES.items():
-                if not hasattr(l, name):
-                    raise _lib.GpHipError(f"{_lib.LIB_PATH} does not export {name} (include/gp_gcn.h): {rebuild}")
-                fn = getattr(l, name)
-                fn.restype, fn.argtypes = restype, argtypes
-            if int(l.gp_gcn_abi_version()) != GP_GCN_ABI_VERSION:
-                raise _lib.GpHipError(f"{_lib.LIB_PATH} implements GCN ABI {int(l.gp_gcn_abi_version())}, this binding is written "
-                                      f"against {GP_GCN_ABI_VERSION} (include/gp_gcn.h): {rebuild}")
-            _bound = l
-    return _bound
+ABI = _lib.Abi("gp_gcn.h", "gp_gcn_abi_version", GP_GCN_ABI_VERSION, PROTOTYPES)
+lib = ABI.lib            # the handle of _lib.lib() with this table applied (once)
 
 
 def _dev(t, name, shape=None):
@@ -192,10 +170,7 @@ def rollout(table, K, T, H, num_stage, output_size, no_mapping, xyz, rot, frames
     xyz_out = torch.empty(rows, K, 3, dtype=torch.float32, device=dev)
     rot_out = torch.empty(rows, K, 4, dtype=torch.float32, device=dev)
     delta_out = torch.empty(rows, K, 7, dtype=torch.float32, device=dev) if base_xyz is not None else None
-    nbytes = int(lib().gp_gcn_scratch_bytes(K, T, H, num_stage, output_size, frames))
-    if nbytes < 0:
-        raise _lib.GpHipError(f"gp_gcn_scratch_bytes: {lib().gp_last_error().decode(errors='replace')}")
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)       # (the caching allocator aligns to 512 bytes)
+    scratch = _lib.scratch(lib().gp_gcn_scratch_bytes, K, T, H, num_stage, output_size, frames, device=dev)
     with _lib.on_device(dev):
         _lib.check(lib().gp_gcn_rollout(K, T, H, num_stage, output_size, int(bool(no_mapping)), table, len(table), xyz, rot, frames,
                                         int(bool(norm_rotation)), base_xyz, xyz_out, rot_out, delta_out, scratch, _lib.stream_ptr(dev)),

@@ -18,7 +18,6 @@ from __future__ import annotations
 import ctypes as C
 import os
 import struct
-import threading
 from concurrent.futures import ThreadPoolExecutor
 from types import SimpleNamespace
 
@@ -52,29 +51,8 @@ def _prototypes():
 
 
 PROTOTYPES = _prototypes()
-_bound = None
-_lock = threading.Lock()
-
-
-def lib() -> C.CDLL:
-    """The handle of _lib.lib() with the decoder's prototypes applied (once)."""
-    global _bound
-    if _bound is not None:
-        return _bound
-    with _lock:
-        if _bound is None:
-            l = _lib.lib()
-            rebuild = "rebuild the library (__graft_entry__.build(force=True))"
-            for name, (restype, argtypes) in PROTOTYPES.items():
-                if not hasattr(l, name):
-                    raise _lib.GpHipError(f"{_lib.LIB_PATH} does not export {name} (include/gp_jpeg_decode.h): {rebuild}")
-                fn = getattr(l, name)
-                fn.restype, fn.argtypes = restype, argtypes
-            if int(l.gp_jpeg_decode_abi_version()) != GP_JPEG_DECODE_ABI_VERSION:
-                raise _lib.GpHipError(f"{_lib.LIB_PATH} implements JPEG-decode ABI {int(l.gp_jpeg_decode_abi_version())}, this binding is "
-                                      f"written against {GP_JPEG_DECODE_ABI_VERSION} (include/gp_jpeg_decode.h): {rebuild}")
-            _bound = l
-    return _bound
+ABI = _lib.Abi("gp_jpeg_decode.h", "gp_jpeg_decode_abi_version", GP_JPEG_DECODE_ABI_VERSION, PROTOTYPES)
+lib = ABI.lib            # the handle of _lib.lib() with this table applied (once)
 
 
 _SOF_NAMES = {0xc1: "extended sequential (SOF1)", 0xc2: "progressive (SOF2)", 0xc3: "lossless (SOF3)", 0xc5: "differential sequential (SOF5)",
@@ -339,10 +317,7 @@ def launch(staged, up, shapes, words, *, device, dtype, guard=0):
     with _lib.on_device(device):
         for ((H, W, sub), idx), pl in zip(shapes, staged.plans):
             B, stride = len(idx), 3 * H * W + int(guard)
-            n = int(l.gp_jpeg_decode_scratch_bytes(B, H, W, sub, len(pl.seg)))
-            if n < 0:
-                raise _lib.GpHipError(f"gp_jpeg_decode_scratch_bytes: {l.gp_last_error().decode(errors='replace')}")
-            scratch = torch.empty(n, dtype=torch.uint8, device=device)          # (the caching allocator aligns to 512 bytes)
+            scratch = _lib.scratch(l.gp_jpeg_decode_scratch_bytes, B, H, W, sub, len(pl.seg), device=device)
             dst = torch.empty(B, stride, dtype=dtype, device=device)
             if guard:
                 dst.view(torch.uint8).fill_(0xA5)

@@ -17,7 +17,6 @@ from __future__ import annotations
 import ctypes as C
 import os
 import struct
-import threading
 from fractions import Fraction
 
 import torch
@@ -50,29 +49,8 @@ def _prototypes():
 
 
 PROTOTYPES = _prototypes()
-_bound = None
-_lock = threading.Lock()
-
-
-def lib() -> C.CDLL:
-    """The handle of _lib.lib() with the JPEG prototypes applied (once)."""
-    global _bound
-    if _bound is not None:
-        return _bound
-    with _lock:
-        if _bound is None:
-            l = _lib.lib()
-            rebuild = "rebuild the library (__graft_entry__.build(force=True))"
-            for name, (restype, argtypes) in PROTOTYPES.items():
-                if not hasattr(l, name):
-                    raise _lib.GpHipError(f"{_lib.LIB_PATH} does not export {name} (include/gp_jpeg.h): {rebuild}")
-                fn = getattr(l, name)
-                fn.restype, fn.argtypes = restype, argtypes
-            if int(l.gp_jpeg_abi_version()) != GP_JPEG_ABI_VERSION:
-                raise _lib.GpHipError(f"{_lib.LIB_PATH} implements JPEG ABI {int(l.gp_jpeg_abi_version())}, this binding is written "
-                                      f"against {GP_JPEG_ABI_VERSION} (include/gp_jpeg.h): {rebuild}")
-            _bound = l
-    return _bound
+ABI = _lib.Abi("gp_jpeg.h", "gp_jpeg_abi_version", GP_JPEG_ABI_VERSION, PROTOTYPES)
+lib = ABI.lib            # the handle of _lib.lib() with this table applied (once)
 
 
 def _sub(subsampling) -> int:
@@ -86,7 +64,7 @@ def quant_tables(quality):
     """(luminance, chrominance): two lists of 64 entries in natural (row-major) order, the Annex K tables scaled by the IJG rule."""
     lum, chr_ = (C.c_uint8 * 64)(), (C.c_uint8 * 64)()
     if lib().gp_jpeg_quant_tables(int(quality), lum, chr_):
-        raise ValueError(f"jpeg_ops.quant_tables: {lib().gp_last_error().decode(errors='replace')}")
+        raise ValueError(f"jpeg_ops.quant_tables: {_lib.last_error()}")
     return list(lum), list(chr_)
 
 
@@ -94,7 +72,7 @@ def bound(H, W, subsampling="420") -> int:
     """The largest file an H x W image can become, in bytes (a multiple of 8); ValueError outside the limits of gp_jpeg.h."""
     n = int(lib().gp_jpeg_bound(int(H), int(W), _sub(subsampling)))
     if n < 0:
-        raise ValueError(f"jpeg_ops.bound: {lib().gp_last_error().decode(errors='replace')}")
+        raise ValueError(f"jpeg_ops.bound: {_lib.last_error()}")
     return n
 
 
@@ -119,16 +97,13 @@ def encode(images, *, quality=90, subsampling="420", qtables=None, out=None):
     B, _, H, W = x.shape
     dev = x.device
     stride = bound(H, W, subsampling)
-    nscratch = int(lib().gp_jpeg_scratch_bytes(B, H, W, sub))
-    if nscratch < 0:
-        raise _lib.GpHipError(f"gp_jpeg_scratch_bytes: {lib().gp_last_error().decode(errors='replace')}")
+    scratch = _lib.scratch(lib().gp_jpeg_scratch_bytes, B, H, W, sub, device=dev)
     if out is None:
         out = torch.empty(B, stride, dtype=torch.uint8, device=dev)
     elif (not torch.is_tensor(out) or out.dtype != torch.uint8 or out.device != dev or out.dim() != 2 or out.shape[0] != B
           or out.shape[1] < stride or not out.is_contiguous()):
         raise RuntimeError(f"jpeg_ops.encode: out must be a contiguous [{B}, >= {stride}] uint8 tensor on {dev}")
     sizes = torch.empty(B, dtype=torch.int32, device=dev)
-    scratch = torch.empty(nscratch, dtype=torch.uint8, device=dev)          # (the caching allocator aligns to 512 bytes)
     with _lib.on_device(dev):
         _lib.check(lib().gp_jpeg_encode(B, H, W, x, SRC_U8 if x.dtype == torch.uint8 else SRC_F32, lum, chr_, sub,
                                         out, out.shape[1], sizes, scratch, _lib.stream_ptr(dev)), "gp_jpeg_encode")
@@ -137,12 +112,7 @@ def encode(images, *, quality=90, subsampling="420", qtables=None, out=None):
 
 def encode_to_bytes(images, *, quality=90, subsampling="420", qtables=None):
     """The files as a list of bytes: one read of the device (the sizes ride behind the buffer in one tensor)."""
-    out, sizes = encode(images, quality=quality, subsampling=subsampling, qtables=qtables)
-    both = torch.cat([out.reshape(-1), sizes.view(torch.uint8)]).cpu()
-    B, stride = out.shape
-    n = both[B * stride:].view(torch.int32).tolist()
-    flat = both.numpy()
-    return [flat[b * stride:b * stride + n[b]].tobytes() for b in range(B)]
+    return png_ops.files_to_bytes(*encode(images, quality=quality, subsampling=subsampling, qtables=qtables))
 
 
 class JpegWriter(png_ops.PngWriter):

@@ -9,7 +9,6 @@ comes back SERIAL (a stream that is not well formed) through the one-lane path, 
 from __future__ import annotations
 
 import ctypes as ct
-import threading
 
 import torch
 
@@ -36,29 +35,8 @@ def _prototypes():
 
 
 PROTOTYPES = _prototypes()
-_bound = None
-_lock = threading.Lock()
-
-
-def lib() -> ct.CDLL:
-    """The handle of _lib.lib() with this stage's prototypes applied (once)."""
-    global _bound
-    if _bound is not None:
-        return _bound
-    with _lock:
-        if _bound is None:
-            l = _lib.lib()
-            rebuild = "rebuild the library (__graft_entry__.build(force=True))"
-            for name, (restype, argtypes) in PROTOTYPES.items():
-                if not hasattr(l, name):
-                    raise _lib.GpHipError(f"{_lib.LIB_PATH} does not export {name} (include/gp_jpeg_sync.h): {rebuild}")
-                fn = getattr(l, name)
-                fn.restype, fn.argtypes = restype, argtypes
-            if int(l.gp_jpeg_sync_abi_version()) != GP_JPEG_SYNC_ABI_VERSION:
-                raise _lib.GpHipError(f"{_lib.LIB_PATH} implements JPEG-sync ABI {int(l.gp_jpeg_sync_abi_version())}, this binding is "
-                                      f"written against {GP_JPEG_SYNC_ABI_VERSION} (include/gp_jpeg_sync.h): {rebuild}")
-            _bound = l
-    return _bound
+ABI = _lib.Abi("gp_jpeg_sync.h", "gp_jpeg_sync_abi_version", GP_JPEG_SYNC_ABI_VERSION, PROTOTYPES)
+lib = ABI.lib            # the handle of _lib.lib() with this table applied (once)
 
 
 def eligible(item) -> bool:
@@ -76,10 +54,8 @@ def launch(staged, up, shapes, words, *, device, dtype, guard=0):
     with _lib.on_device(device):
         for ((H, W, sub), idx), pl in zip(shapes, staged.plans):
             B, stride = len(idx), 3 * H * W + guard
-            n = int(l.gp_jpeg_sync_scratch_bytes(B, H, W, sub, pl.bytes))
-            if n < 0:
-                raise _lib.GpHipError(f"gp_jpeg_sync_scratch_bytes: {l.gp_last_error().decode(errors='replace')}")
-            scratch = torch.empty(n + 2 * pad, dtype=torch.uint8, device=device)          # (the caching allocator aligns to 512 bytes)
+            scratch = _lib.scratch(l.gp_jpeg_sync_scratch_bytes, B, H, W, sub, pl.bytes, device=device, extra=2 * pad)
+            n = scratch.numel() - 2 * pad
             dst = torch.empty(B, stride, dtype=dtype, device=device)
             if guard:
                 dst.view(torch.uint8).fill_(0xA5)

@@ -9,7 +9,6 @@ No kernel uses a float atomic: two calls on equal inputs give equal bits.  Nothi
 from __future__ import annotations
 
 import ctypes as C
-import threading
 
 import torch
 
@@ -34,29 +33,8 @@ def _prototypes():
 
 
 PROTOTYPES = _prototypes()
-_bound = None
-_lock = threading.Lock()
-
-
-def lib() -> C.CDLL:
-    """The handle of _lib.lib() with the k-means prototypes applied (once)."""
-    global _bound
-    if _bound is not None:
-        return _bound
-    with _lock:
-        if _bound is None:
-            l = _lib.lib()
-            rebuild = "rebuild the library (__graft_entry__.build(force=True))"
-            for name, (restype, argtypes) in PROTOTYPES.items():
-                if not hasattr(l, name):
-                    raise _lib.GpHipError(f"{_lib.LIB_PATH} does not export {name} (include/gp_kmeans.h): {rebuild}")
-                fn = getattr(l, name)
-                fn.restype, fn.argtypes = restype, argtypes
-            if int(l.gp_kmeans_abi_version()) != GP_KMEANS_ABI_VERSION:
-                raise _lib.GpHipError(f"{_lib.LIB_PATH} implements k-means ABI {int(l.gp_kmeans_abi_version())}, this binding is written "
-                                      f"against {GP_KMEANS_ABI_VERSION} (include/gp_kmeans.h): {rebuild}")
-            _bound = l
-    return _bound
+ABI = _lib.Abi("gp_kmeans.h", "gp_kmeans_abi_version", GP_KMEANS_ABI_VERSION, PROTOTYPES)
+lib = ABI.lib            # the handle of _lib.lib() with this table applied (once)
 
 
 def _device_rows(t, name, dtypes=(torch.float32,), cols=None):
@@ -87,10 +65,7 @@ def _check_k(K):
 
 
 def _scratch(n, d, k, dev):
-    nbytes = int(lib().gp_kmeans_scratch_bytes(n, d, k))
-    if nbytes < 0:
-        raise _lib.GpHipError(f"gp_kmeans_scratch_bytes: {lib().gp_last_error().decode(errors='replace')}")
-    return torch.empty(nbytes, dtype=torch.uint8, device=dev)       # (the caching allocator aligns to 512 bytes)
+    return _lib.scratch(lib().gp_kmeans_scratch_bytes, n, d, k, device=dev)
 
 
 def assign(X, centres, return_d2=False):

@@ -12,7 +12,6 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-import threading
 from types import SimpleNamespace
 
 import torch
@@ -45,29 +44,8 @@ def _prototypes():
 
 
 PROTOTYPES = _prototypes()
-_bound = None
-_lock = threading.Lock()
-
-
-def lib() -> C.CDLL:
-    """The handle of _lib.lib() with the LPIPS prototypes applied (once)."""
-    global _bound
-    if _bound is not None:
-        return _bound
-    with _lock:
-        if _bound is None:
-            l = _lib.lib()
-            rebuild = "rebuild the library (__graft_entry__.build(force=True))"
-            for name, (restype, argtypes) in PROTOTYPES.items():
-                if not hasattr(l, name):
-                    raise _lib.GpHipError(f"{_lib.LIB_PATH} does not export {name} (include/gp_lpips.h): {rebuild}")
-                fn = getattr(l, name)
-                fn.restype, fn.argtypes = restype, argtypes
-            if int(l.gp_lpips_abi_version()) != GP_LPIPS_ABI_VERSION:
-                raise _lib.GpHipError(f"{_lib.LIB_PATH} implements LPIPS ABI {int(l.gp_lpips_abi_version())}, this binding is written against "
-                                      f"{GP_LPIPS_ABI_VERSION} (include/gp_lpips.h): {rebuild}")
-            _bound = l
-    return _bound
+ABI = _lib.Abi("gp_lpips.h", "gp_lpips_abi_version", GP_LPIPS_ABI_VERSION, PROTOTYPES)
+lib = ABI.lib            # the handle of _lib.lib() with this table applied (once)
 
 
 def _net_id(net_type):
@@ -84,7 +62,7 @@ def network_table(net_type):
     net, l = _net_id(net_type), lib()
     n = int(l.gp_lpips_num_layers(net))
     if n < 0:
-        raise _lib.GpHipError(f"gp_lpips_num_layers: {l.gp_last_error().decode(errors='replace')}")
+        raise _lib.GpHipError(f"gp_lpips_num_layers: {_lib.last_error()}")
     out = []
     for i in range(n):
         d = (C.c_int32 * 8)()
@@ -176,12 +154,9 @@ class LPIPS:
         key = (_lib.stream_ptr(self.device).value, H, W)
         t = self._scratch.get(key)
         if t is None:
-            n = int(lib().gp_lpips_scratch_bytes(self.net, 1, H, W))
-            if n < 0:
-                raise _lib.GpHipError(f"gp_lpips_scratch_bytes: {lib().gp_last_error().decode(errors='replace')}")
             if len(self._scratch) >= 2:
                 self._scratch.pop(next(iter(self._scratch)))
-            t = torch.empty(n + 256, dtype=torch.uint8, device=self.device)
+            t = _lib.scratch(lib().gp_lpips_scratch_bytes, self.net, 1, H, W, device=self.device, extra=256)
             self._scratch[key] = t
         return t
 

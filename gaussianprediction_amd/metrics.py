@@ -36,10 +36,7 @@ def metrics_scratch(device, B, H, W, flags):
     key = (device.index, _lib.stream_ptr(device).value, B, H, W, flags)
     t = _scratch.get(key)
     if t is None:
-        n = int(_lib.lib().gp_image_metrics_scratch_bytes(B, H, W, flags))
-        if n < 0:
-            raise _lib.GpHipError(f"gp_image_metrics_scratch_bytes: {_lib.lib().gp_last_error().decode(errors='replace')}")
-        t = torch.empty(n + 256, dtype=torch.uint8, device=device)
+        t = _lib.scratch(_lib.lib().gp_image_metrics_scratch_bytes, B, H, W, flags, device=device, extra=256)
         if len(_scratch) >= 16:
             _scratch.pop(next(iter(_scratch)))
         _scratch[key] = t

@@ -16,7 +16,6 @@ from __future__ import annotations
 import ctypes as C
 import os
 import struct
-import threading
 import zlib
 from concurrent.futures import ThreadPoolExecutor
 from types import SimpleNamespace
@@ -53,29 +52,8 @@ def _prototypes():
 
 
 PROTOTYPES = _prototypes()
-_bound = None
-_lock = threading.Lock()
-
-
-def lib() -> C.CDLL:
-    """The handle of _lib.lib() with the decoder's prototypes applied (once)."""
-    global _bound
-    if _bound is not None:
-        return _bound
-    with _lock:
-        if _bound is None:
-            l = _lib.lib()
-            rebuild = "rebuild the library (__graft_entry__.build(force=True))"
-            for name, (restype, argtypes) in PROTOTYPES.items():
-                if not hasattr(l, name):
-                    raise _lib.GpHipError(f"{_lib.LIB_PATH} does not export {name} (include/gp_png_decode.h): {rebuild}")
-                fn = getattr(l, name)
-                fn.restype, fn.argtypes = restype, argtypes
-            if int(l.gp_png_decode_abi_version()) != GP_PNG_DECODE_ABI_VERSION:
-                raise _lib.GpHipError(f"{_lib.LIB_PATH} implements PNG-decode ABI {int(l.gp_png_decode_abi_version())}, this binding is "
-                                      f"written against {GP_PNG_DECODE_ABI_VERSION} (include/gp_png_decode.h): {rebuild}")
-            _bound = l
-    return _bound
+ABI = _lib.Abi("gp_png_decode.h", "gp_png_decode_abi_version", GP_PNG_DECODE_ABI_VERSION, PROTOTYPES)
+lib = ABI.lib            # the handle of _lib.lib() with this table applied (once)
 
 
 def parse(data, name="<bytes>"):
@@ -237,10 +215,7 @@ def launch(staged, up, shapes, words, *, device, dtype, background, guard=0):
     with _lib.on_device(device):
         for ((H, W, Cn), c_out, idx), pl in zip(shapes, staged.plans):
             B, stride = len(idx), c_out * H * W + int(guard)
-            n = int(l.gp_png_decode_scratch_bytes(B, H, W, Cn, len(pl.seg)))
-            if n < 0:
-                raise _lib.GpHipError(f"gp_png_decode_scratch_bytes: {l.gp_last_error().decode(errors='replace')}")
-            scratch = torch.empty(n, dtype=torch.uint8, device=device)          # (the caching allocator aligns to 512 bytes)
+            scratch = _lib.scratch(l.gp_png_decode_scratch_bytes, B, H, W, Cn, len(pl.seg), device=device)
             dst = torch.empty(B, stride, dtype=dtype, device=device)
             if guard:
                 dst.view(torch.uint8).fill_(0xA5)

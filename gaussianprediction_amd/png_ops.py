@@ -33,36 +33,15 @@ def _prototypes():
 
 
 PROTOTYPES = _prototypes()
-_bound = None
-_lock = threading.Lock()
-
-
-def lib() -> C.CDLL:
-    """The handle of _lib.lib() with the PNG prototypes applied (once)."""
-    global _bound
-    if _bound is not None:
-        return _bound
-    with _lock:
-        if _bound is None:
-            l = _lib.lib()
-            rebuild = "rebuild the library (__graft_entry__.build(force=True))"
-            for name, (restype, argtypes) in PROTOTYPES.items():
-                if not hasattr(l, name):
-                    raise _lib.GpHipError(f"{_lib.LIB_PATH} does not export {name} (include/gp_png.h): {rebuild}")
-                fn = getattr(l, name)
-                fn.restype, fn.argtypes = restype, argtypes
-            if int(l.gp_png_abi_version()) != GP_PNG_ABI_VERSION:
-                raise _lib.GpHipError(f"{_lib.LIB_PATH} implements PNG ABI {int(l.gp_png_abi_version())}, this binding is written "
-                                      f"against {GP_PNG_ABI_VERSION} (include/gp_png.h): {rebuild}")
-            _bound = l
-    return _bound
+ABI = _lib.Abi("gp_png.h", "gp_png_abi_version", GP_PNG_ABI_VERSION, PROTOTYPES)
+lib = ABI.lib            # the handle of _lib.lib() with this table applied (once)
 
 
 def bound(H, W) -> int:
     """The largest file an H x W image can become, in bytes (a multiple of 8); ValueError outside the limits of gp_png.h."""
     n = int(lib().gp_png_bound(int(H), int(W)))
     if n < 0:
-        raise ValueError(f"png_ops.bound: {lib().gp_last_error().decode(errors='replace')}")
+        raise ValueError(f"png_ops.bound: {_lib.last_error()}")
     return n
 
 
@@ -106,16 +85,13 @@ def encode(images, *, filter_none=False, out=None):
     B, _, H, W = x.shape
     dev = x.device
     stride = bound(H, W)
-    nscratch = int(lib().gp_png_scratch_bytes(B, H, W))
-    if nscratch < 0:
-        raise _lib.GpHipError(f"gp_png_scratch_bytes: {lib().gp_last_error().decode(errors='replace')}")
+    scratch = _lib.scratch(lib().gp_png_scratch_bytes, B, H, W, device=dev)
     if out is None:
         out = torch.empty(B, stride, dtype=torch.uint8, device=dev)
     elif (not torch.is_tensor(out) or out.dtype != torch.uint8 or out.device != dev or out.dim() != 2 or out.shape[0] != B
           or out.shape[1] < stride or not out.is_contiguous()):
         raise RuntimeError(f"png_ops.encode: out must be a contiguous [{B}, >= {stride}] uint8 tensor on {dev}")
     sizes = torch.empty(B, dtype=torch.int32, device=dev)
-    scratch = torch.empty(nscratch, dtype=torch.uint8, device=dev)          # (the caching allocator aligns to 512 bytes)
     with _lib.on_device(dev):
         _lib.check(lib().gp_png_encode(B, H, W, x, SRC_U8 if x.dtype == torch.uint8 else SRC_F32, FILTER_NONE if filter_none else 0,
                                        out, out.shape[1], sizes, scratch, _lib.stream_ptr(dev)), "gp_png_encode")
@@ -124,7 +100,11 @@ def encode(images, *, filter_none=False, out=None):
 
 def encode_to_bytes(images, *, filter_none=False):
     """The files as a list of bytes: one read of the device (the sizes ride behind the buffer in one tensor)."""
-    out, sizes = encode(images, filter_none=filter_none)
+    return files_to_bytes(*encode(images, filter_none=filter_none))
+
+
+def files_to_bytes(out, sizes):
+    """What `encode` (here or in jpeg_ops) returned, as a list of bytes, with one read of the device."""
     both = torch.cat([out.reshape(-1), sizes.view(torch.uint8)]).cpu()
     B, stride = out.shape
     n = both[B * stride:].view(torch.int32).tolist()

@@ -130,7 +130,7 @@ class WeightsModel(nn.Module):
         self.cfg = HashGridConfigC(n_levels, n_features_per_level, log2_hashmap_size, base_resolution, per_level_scale)
         entries = int(_lib.lib().gp_hashgrid_table_entries(self.cfg))
         if entries < 0:
-            raise RuntimeError(_lib.lib().gp_last_error().decode(errors='replace'))
+            raise RuntimeError(_lib.last_error())
         self.table_entries = entries
         gen = torch.Generator().manual_seed(seed)
 

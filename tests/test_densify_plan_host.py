@@ -2,21 +2,19 @@
 CPU GaussianModel, bit for bit (this pins what the device path of tests/test_gpu_densify_device.py is compared with to current
 behaviour); include/gp_densify.h against the binding's table; the refusals that need no device."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
 import pytest
 import torch
 
+import abi_check
 import densify_ref as R
 import gaussianprediction_amd as gpa
 from gaussianprediction_amd import _lib, densify_ops as D
 from gaussianprediction_amd.scene_synth import SceneSpec, make_gaussians
 from gaussianprediction_amd.training import default_training_args
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 TH = dict(grad_threshold=0.0002, percent_dense=0.01, extent=5.0, min_opacity=0.005)
 
 
@@ -120,48 +118,16 @@ _SCALARS = {"int": C.c_int32, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint3
 _POINTEES = {"float", "void", "int32_t", "uint32_t", "uint8_t", "gp_densify_tensor"}
 
 
-def _header():
-    hdr = open(os.path.join(ROOT, "include", "gp_densify.h")).read()
-    return re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
-
-
-def _header_prototypes():
-    hdr = re.sub(r"typedef struct.*?\}\s*\w+;", "", _header(), flags=re.S)
-    hdr = re.sub(r"^\s*#.*$", "", hdr, flags=re.M)
-    protos = {}
-    for ret, name, params in re.findall(r"([A-Za-z_][\w\s\*]*?)\b(gp_[a-z_0-9]+)\s*\(([^;{]*?)\)\s*;", hdr):
-        assert name not in protos, name
-        params = " ".join(params.split())
-        plist = [] if params in ("", "void") else [re.sub(r"\s*\w+$", "", p.strip()) for p in params.split(",")]
-        protos[name] = (" ".join(ret.split()), [" ".join(t.replace("const", " ").replace("*", " * ").split()) for t in plist])
-    return protos
-
-
 def test_prototype_table_equals_the_header():
-    protos = _header_prototypes()
-    assert set(protos) == set(D.PROTOTYPES), set(protos) ^ set(D.PROTOTYPES)
-    assert len(protos) == 5
-    for name, (ret, params) in protos.items():
-        restype, argtypes = D.PROTOTYPES[name]
-        assert restype is {"int": C.c_int32, "int64_t": C.c_int64}[ret], (name, ret, restype)
-        assert len(argtypes) == len(params), (name, params, argtypes)
-        for k, (ctype, cls) in enumerate(zip(params, argtypes)):
-            if "*" in ctype:
-                assert ctype.split("*")[0].strip() in _POINTEES and cls is _lib.Ptr, (name, k, ctype, cls)
-            else:
-                assert cls is _SCALARS[ctype], (name, k, ctype, cls)
-    assert not set(protos) & set(_lib.PROTOTYPES)            # none of them leaks into the main ABI's table
+    abi_check.check_table(D.ABI, 5, _SCALARS, _POINTEES)
+    assert D.ABI.prototypes is D.PROTOTYPES and D.ABI.header == "gp_densify.h"
 
 
 def test_symbols_constants_and_the_table_entry_layout():
-    hdr = _header()
+    hdr = abi_check.header_text("gp_densify.h")
     defs = {k: int(v) for k, v in re.findall(r"#define (GP_DENSIFY_[A-Z0-9_]+) (\d+)u?\b", hdr)}
-    assert defs["GP_DENSIFY_ABI_VERSION"] == D.GP_DENSIFY_ABI_VERSION == 1
-    l = D.lib()
-    assert l is _lib.lib() and int(l.gp_densify_abi_version()) == 1
-    for name, (restype, argtypes) in D.PROTOTYPES.items():
-        fn = getattr(l, name)
-        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
+    assert defs["GP_DENSIFY_ABI_VERSION"] == D.GP_DENSIFY_ABI_VERSION == D.ABI.version == 1
+    l = abi_check.check_applied(D.ABI)
     assert (defs["GP_DENSIFY_BLOCK"], defs["GP_DENSIFY_MAX_TENSORS"], defs["GP_DENSIFY_MAX_ROWS"]) == (D.BLOCK, D.MAX_TENSORS, D.MAX_ROWS)
     assert tuple(defs["GP_DENSIFY_" + k] for k in ("DENSIFY", "RESET", "PRUNE", "SCREEN")) == (D.DENSIFY, D.RESET, D.PRUNE, D.SCREEN)
     assert tuple(defs["GP_DENSIFY_ST_" + k] for k in ("CLONED", "SPLIT", "PRUNED", "ROWS", "BASE")) == \

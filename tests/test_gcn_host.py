@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 import torch
 
+import abi_check
 import gcn_ref as R
 from gaussianprediction_amd import _lib, gcn_ops as G, motion
 
@@ -58,45 +59,17 @@ _SCALARS = {"int": C.c_int32, "int32_t": C.c_int32, "int64_t": C.c_int64, "gp_st
 _POINTEES = {"float", "void"}
 
 
-def _header():
-    return re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "gp_gcn.h")).read(), flags=re.S)
-
-
-def _header_prototypes():
-    hdr = re.sub(r"^\s*#.*$", "", _header(), flags=re.M)
-    protos = {}
-    for ret, name, params in re.findall(r"([A-Za-z_][\w\s\*]*?)\b(gp_[a-z_0-9]+)\s*\(([^;{]*?)\)\s*;", hdr):
-        assert name not in protos, name
-        params = " ".join(params.split())
-        plist = [] if params in ("", "void") else [re.sub(r"\s*\w+$", "", p.strip()) for p in params.split(",")]
-        protos[name] = (" ".join(ret.split()), [" ".join(t.replace("const", " ").replace("*", " * ").split()) for t in plist])
-    return protos
-
-
 def test_prototype_table_equals_the_header():
-    protos = _header_prototypes()
-    assert set(protos) == set(G.PROTOTYPES) and len(protos) == 5, set(protos) ^ set(G.PROTOTYPES)
-    for name, (ret, params) in protos.items():
-        restype, argtypes = G.PROTOTYPES[name]
-        assert restype is {"int": C.c_int32, "int64_t": C.c_int64}[ret], (name, ret)
-        assert len(argtypes) == len(params), (name, len(params), len(argtypes))
-        for k, (ctype, cls) in enumerate(zip(params, argtypes)):
-            if "*" in ctype:
-                assert ctype.split("*")[0].strip() in _POINTEES and cls is _lib.Ptr, (name, k, ctype, cls)
-            else:
-                assert cls is _SCALARS[ctype], (name, k, ctype, cls)
+    protos = abi_check.check_table(G.ABI, 5, _SCALARS, _POINTEES)
+    assert G.ABI.prototypes is G.PROTOTYPES and G.ABI.header == "gp_gcn.h"
+    for name, (_, params) in protos.items():
         assert params == [] or params[-1] == "gp_stream_t" or name == "gp_gcn_scratch_bytes", name
-    assert not set(protos) & set(_lib.PROTOTYPES)
 
 
 def test_symbols_and_constants():
-    defs = {k: int(v) for k, v in re.findall(r"#define (GP_GCN_[A-Z0-9_]+) (\d+)\b", _header())}
-    assert defs["GP_GCN_ABI_VERSION"] == G.GP_GCN_ABI_VERSION == 1
-    l = G.lib()
-    assert l is _lib.lib() and int(l.gp_gcn_abi_version()) == 1
-    for name, (restype, argtypes) in G.PROTOTYPES.items():
-        fn = getattr(l, name)
-        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
+    defs = {k: int(v) for k, v in re.findall(r"#define (GP_GCN_[A-Z0-9_]+) (\d+)\b", abi_check.header_text("gp_gcn.h"))}
+    assert defs["GP_GCN_ABI_VERSION"] == G.GP_GCN_ABI_VERSION == G.ABI.version == 1
+    abi_check.check_applied(G.ABI)
     assert (defs["GP_GCN_MAX_M"], defs["GP_GCN_MAX_F"], defs["GP_GCN_MAX_B"], defs["GP_GCN_MAX_FRAMES"], defs["GP_GCN_MAX_STAGES"]) == \
         (G.MAX_M, G.MAX_F, G.MAX_B, G.MAX_FRAMES, G.MAX_STAGES) == (4096, 512, 1024, 4096, 16)
     assert (defs["GP_GCN_ACT_NONE"], defs["GP_GCN_ACT_TANH"], defs["GP_GCN_ACT_RELU"]) == (G.ACT_NONE, G.ACT_TANH, G.ACT_RELU)

@@ -7,6 +7,7 @@ import re
 import pytest
 import torch
 
+import abi_check
 import gaussianprediction_amd as gpa
 from gaussianprediction_amd import _lib
 
@@ -256,55 +257,32 @@ _SCALARS = {"int": C.c_int32, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint3
 _POINTEES = {"float", "double", "void", "int", "int8_t", "int16_t", "int32_t", "int64_t", "uint8_t", "uint16_t", "uint32_t", "uint64_t"}
 
 
-def _header_prototypes():
-    """{name: (return type, [parameter type])} of include/gp_hip.h, types as text without `const` and the parameter name."""
-    hdr = open(os.path.join(ROOT, "include", "gp_hip.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
-    hdr = re.sub(r"^\s*#.*$", "", hdr, flags=re.M)
-    hdr = re.sub(r"typedef struct \w*\s*\{.*?\}\s*\w+\s*;", "", hdr, flags=re.S)
-    hdr = re.sub(r"enum\s*\{.*?\}\s*;", "", hdr, flags=re.S)
-    protos = {}
-    for ret, name, params in re.findall(r"([A-Za-z_][\w\s\*]*?)\b(gp_[a-z_0-9]+)\s*\(([^;{]*?)\)\s*;", hdr):
-        assert name not in protos, name
-        params = " ".join(params.split())
-        plist = [] if params in ("", "void") else [re.sub(r"\s*\w+$", "", p.strip()) for p in params.split(",")]
-        protos[name] = (" ".join(ret.split()), [" ".join(t.replace("const", " ").replace("*", " * ").split()) for t in plist])
-    return protos
-
-
-def _class_of(ctype):
-    """The argtypes class section 1 of the binding's rules gives a parameter of C type `ctype`."""
-    if "*" not in ctype:
-        return _SCALARS[ctype]
-    base = ctype.split("*")[0].strip()
-    if base in _STRUCTS:
-        assert ctype == base + " *", ctype
-        return C.POINTER(getattr(_lib, _STRUCTS[base]))
-    assert base in _POINTEES, ctype
-    return _lib.Ptr
+def _abis():
+    """Every registered binding: the nine further modules join _lib.ABIS when they are imported."""
+    from gaussianprediction_amd import (densify_ops, gcn_ops, jpeg_decode, jpeg_ops, jpeg_sync, kmeans_ops, lpips,  # noqa: F401
+                                        png_decode, png_ops)
+    return _lib.ABIS
 
 
 def test_prototype_table_equals_the_header():
-    protos = _header_prototypes()
-    assert set(protos) == set(_lib.PROTOTYPES) == set(_lib.EXPORTS), set(protos) ^ set(_lib.PROTOTYPES)
-    assert len(protos) == len(_lib.EXPORTS) == 64
-    for name, (ret, params) in protos.items():
-        restype, argtypes = _lib.PROTOTYPES[name]
-        assert restype is {"int": C.c_int32, "int64_t": C.c_int64, "const char*": C.c_char_p}[ret], (name, ret, restype)
-        assert len(argtypes) == len(params), (name, params, argtypes)
-        for k, (ctype, cls) in enumerate(zip(params, argtypes)):
-            assert cls is _class_of(ctype), (name, k, ctype, cls)
+    assert _lib.ABIS[0] is _lib.ABI and _lib.ABI.prototypes is _lib.PROTOTYPES and _lib.ABI.version == _lib.GP_ABI_VERSION
+    protos = abi_check.check_table(_lib.ABI, 64, _SCALARS, _POINTEES, {c: getattr(_lib, py) for c, py in _STRUCTS.items()})
+    assert set(protos) == set(_lib.EXPORTS) and len(_lib.EXPORTS) == 64
     assert _lib.PROTOTYPES["gp_raster_forward"][1][0]._type_ is _lib.RasterSettingsC           # (POINTER(X) is cached: `is` compares X)
     from gaussianprediction_amd import weights_ops
     assert weights_ops.HashGridConfigC is _lib.HashGridConfigC
 
 
 def test_prototype_table_is_applied_to_the_library():
-    l = _lib.lib()
-    for name, (restype, argtypes) in _lib.PROTOTYPES.items():
-        fn = getattr(l, name)
-        assert fn.restype is restype, name
-        assert list(fn.argtypes) == list(argtypes), name
+    abi_check.check_applied(_lib.ABI)
+
+
+def test_every_header_has_one_binding_and_no_name_two():
+    abis = _abis()
+    headers = sorted(a.header for a in abis)
+    assert headers == sorted(f for f in os.listdir(os.path.join(ROOT, "include")) if f.endswith(".h")), headers
+    names = [n for a in abis for n in a.prototypes]
+    assert len(names) == len(set(names)) == 106, sorted(n for n in set(names) if names.count(n) > 1)
 
 
 def test_argument_width_survives_without_a_wrapper():
@@ -342,22 +320,38 @@ def test_wrong_argument_kinds_are_refused_before_the_library_runs():
 
 
 def test_every_call_site_passes_as_many_arguments_as_the_prototype_has():
-    """ctypes accepts surplus positional arguments in silence and most call sites only run on a GPU: count them in the source."""
+    """ctypes accepts surplus positional arguments in silence and most call sites only run on a GPU: count them in the source, for
+    every registered table.  A call site is `x.gp_name(...)`, `q(...)` where the file binds `q = x.gp_name`, and
+    `_lib.scratch(x.gp_name, ...)`, which calls its first argument with the further positional ones."""
     import ast
     import glob
+    table = {name: (abi, len(argtypes)) for abi in _abis() for name, (_, argtypes) in abi.prototypes.items()}
     files = [os.path.join(ROOT, "bench.py"), os.path.join(ROOT, "__graft_entry__.py")]
     for d in ("gaussianprediction_amd", "tools", "tests"):
         files += glob.glob(os.path.join(ROOT, d, "**", "*.py"), recursive=True)
-    examined = 0
+    examined = {abi.header: 0 for abi in _abis()}
     for path in sorted(files):
-        for node in ast.walk(ast.parse(open(path).read(), path)):
-            if isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr in _lib.PROTOTYPES:
-                assert not node.keywords, (path, node.lineno)
-                if any(isinstance(a, ast.Starred) for a in node.args):
+        nodes, alias = list(ast.walk(ast.parse(open(path).read(), path))), {}
+        for node in nodes:
+            if isinstance(node, ast.Assign) and isinstance(node.value, ast.Attribute) and node.value.attr in table:
+                for target in node.targets:
+                    if isinstance(target, ast.Name):
+                        assert alias.setdefault(target.id, node.value.attr) == node.value.attr, (path, node.lineno)
+        for node in nodes:
+            if not isinstance(node, ast.Call):
+                continue
+            f, args, keywords = node.func, node.args, node.keywords
+            name = f.attr if isinstance(f, ast.Attribute) else alias.get(f.id) if isinstance(f, ast.Name) else None
+            if name == "scratch" and args and isinstance(args[0], ast.Attribute):
+                name, args, keywords = args[0].attr, args[1:], []
+            if name in table:
+                abi, want = table[name]
+                assert not keywords, (path, node.lineno)
+                if any(isinstance(a, ast.Starred) for a in args):
                     continue
-                examined += 1
-                assert len(node.args) == len(_lib.PROTOTYPES[node.func.attr][1]), (os.path.relpath(path, ROOT), node.lineno, node.func.attr)
-    assert examined >= 100, examined
+                examined[abi.header] += 1
+                assert len(args) == want, (os.path.relpath(path, ROOT), node.lineno, name)
+    assert sum(examined.values()) >= 300 and all(examined.values()), examined
 
 
 def test_allocator_block_releases_on_every_path_and_prefers_the_callback_error():

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+import abi_check
 import jpeg_cases as J
 import jpeg_decode_cases as D
 import jpeg_decode_ref as REF
@@ -20,49 +21,21 @@ import jpeg_ref as R
 from gaussianprediction_amd import _lib, jpeg_decode as JD
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 
 _SCALARS = {"int": C.c_int32, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint32_t": C.c_uint32, "gp_stream_t": _lib.Ptr}
 _POINTEES = {"void", "uint8_t", "uint32_t", "int64_t", "int32_t", "float"}
 
 
-def _header():
-    hdr = open(os.path.join(ROOT, "include", "gp_jpeg_decode.h")).read()
-    return re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
-
-
 def test_prototype_table_equals_the_header():
-    hdr = re.sub(r"^\s*#.*$", "", _header(), flags=re.M)
-    protos = {}
-    for ret, name, params in re.findall(r"([A-Za-z_][\w\s\*]*?)\b(gp_[a-z_0-9]+)\s*\(([^;{]*?)\)\s*;", hdr):
-        assert name not in protos, name
-        params = " ".join(params.split())
-        plist = [] if params in ("", "void") else [re.sub(r"\s*\w+$", "", p.strip()) for p in params.split(",")]
-        protos[name] = (" ".join(ret.split()), [" ".join(t.replace("const", " ").replace("*", " * ").split()) for t in plist])
-    assert set(protos) == set(JD.PROTOTYPES) and len(protos) == 3
-    for name, (ret, params) in protos.items():
-        restype, argtypes = JD.PROTOTYPES[name]
-        assert restype is {"int": C.c_int32, "int64_t": C.c_int64}[ret], (name, ret, restype)
-        assert len(argtypes) == len(params), (name, params, argtypes)
-        for k, (ctype, cls) in enumerate(zip(params, argtypes)):
-            if "*" in ctype:
-                assert ctype.split("*")[0].strip() in _POINTEES and cls is _lib.Ptr, (name, k, ctype, cls)
-            else:
-                assert cls is _SCALARS[ctype], (name, k, ctype, cls)
+    protos = abi_check.check_table(JD.ABI, 3, _SCALARS, _POINTEES)
+    assert JD.ABI.prototypes is JD.PROTOTYPES and JD.ABI.header == "gp_jpeg_decode.h"
     assert protos["gp_jpeg_decode"][1][-1] == "gp_stream_t"        # the stream is the last parameter
-    assert not set(protos) & set(_lib.PROTOTYPES)                  # none of them leaks into the main ABI's table
-    from gaussianprediction_amd import jpeg_ops, png_decode
-    assert not set(protos) & (set(jpeg_ops.PROTOTYPES) | set(png_decode.PROTOTYPES))      # nor into the encoder's or the PNG decoder's
 
 
 def test_symbols_and_constants():
-    defs = {k: int(v) for k, v in re.findall(r"#define (GP_JPEG_DECODE_[A-Z0-9_]+) (\d+)u?\b", _header())}
-    assert defs["GP_JPEG_DECODE_ABI_VERSION"] == JD.GP_JPEG_DECODE_ABI_VERSION == 1
-    l = JD.lib()
-    assert l is _lib.lib() and int(l.gp_jpeg_decode_abi_version()) == 1
-    for name, (restype, argtypes) in JD.PROTOTYPES.items():
-        fn = getattr(l, name)
-        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
+    defs = {k: int(v) for k, v in re.findall(r"#define (GP_JPEG_DECODE_[A-Z0-9_]+) (\d+)u?\b", abi_check.header_text("gp_jpeg_decode.h"))}
+    assert defs["GP_JPEG_DECODE_ABI_VERSION"] == JD.GP_JPEG_DECODE_ABI_VERSION == JD.ABI.version == 1
+    abi_check.check_applied(JD.ABI)
     assert (defs["GP_JPEG_DECODE_MAX_BATCH"], defs["GP_JPEG_DECODE_TABLE_BYTES"], defs["GP_JPEG_DECODE_DST_U8"], defs["GP_JPEG_DECODE_DST_F32"]) \
         == (JD.MAX_BATCH, JD.TABLE_BYTES, JD.DST_U8, JD.DST_F32) == (65535, 1232, 0, 1)
     other = {"ABI_VERSION", "MAX_BATCH", "TABLE_BYTES", "DST_U8", "DST_F32"}

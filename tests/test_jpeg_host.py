@@ -17,6 +17,7 @@ import pytest
 import torch
 from PIL import Image
 
+import abi_check
 import jpeg_cases as J
 import jpeg_ref as R
 import png_cases as P
@@ -51,47 +52,16 @@ _SCALARS = {"int": C.c_int32, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint3
 _POINTEES = {"void", "uint8_t", "uint32_t"}
 
 
-def _header():
-    hdr = open(os.path.join(ROOT, "include", "gp_jpeg.h")).read()
-    return re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
-
-
-def _header_prototypes():
-    hdr = re.sub(r"^\s*#.*$", "", _header(), flags=re.M)
-    protos = {}
-    for ret, name, params in re.findall(r"([A-Za-z_][\w\s\*]*?)\b(gp_[a-z_0-9]+)\s*\(([^;{]*?)\)\s*;", hdr):
-        assert name not in protos, name
-        params = " ".join(params.split())
-        plist = [] if params in ("", "void") else [re.sub(r"\s*\w+$", "", p.strip()) for p in params.split(",")]
-        protos[name] = (" ".join(ret.split()), [" ".join(t.replace("const", " ").replace("*", " * ").split()) for t in plist])
-    return protos
-
-
 def test_prototype_table_equals_the_header():
-    protos = _header_prototypes()
-    assert set(protos) == set(JPG.PROTOTYPES), set(protos) ^ set(JPG.PROTOTYPES)
-    assert len(protos) == 5
-    for name, (ret, params) in protos.items():
-        restype, argtypes = JPG.PROTOTYPES[name]
-        assert restype is {"int": C.c_int32, "int64_t": C.c_int64}[ret], (name, ret, restype)
-        assert len(argtypes) == len(params), (name, params, argtypes)
-        for k, (ctype, cls) in enumerate(zip(params, argtypes)):
-            if "*" in ctype:
-                assert ctype.split("*")[0].strip() in _POINTEES and cls is _lib.Ptr, (name, k, ctype, cls)
-            else:
-                assert cls is _SCALARS[ctype], (name, k, ctype, cls)
+    protos = abi_check.check_table(JPG.ABI, 5, _SCALARS, _POINTEES)
+    assert JPG.ABI.prototypes is JPG.PROTOTYPES and JPG.ABI.header == "gp_jpeg.h"
     assert protos["gp_jpeg_encode"][1][-1] == "gp_stream_t"        # the stream is the last parameter
-    assert not set(protos) & set(_lib.PROTOTYPES)                  # none of them leaks into the main ABI's table
 
 
 def test_symbols_and_constants():
-    defs = {k: int(v) for k, v in re.findall(r"#define (GP_JPEG_[A-Z0-9_]+) (\d+)u?\b", _header())}
-    assert defs["GP_JPEG_ABI_VERSION"] == JPG.GP_JPEG_ABI_VERSION == 1
-    l = JPG.lib()
-    assert l is _lib.lib() and int(l.gp_jpeg_abi_version()) == 1
-    for name, (restype, argtypes) in JPG.PROTOTYPES.items():
-        fn = getattr(l, name)
-        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
+    defs = {k: int(v) for k, v in re.findall(r"#define (GP_JPEG_[A-Z0-9_]+) (\d+)u?\b", abi_check.header_text("gp_jpeg.h"))}
+    assert defs["GP_JPEG_ABI_VERSION"] == JPG.GP_JPEG_ABI_VERSION == JPG.ABI.version == 1
+    abi_check.check_applied(JPG.ABI)
     assert (defs["GP_JPEG_RESTART_MCUS"], defs["GP_JPEG_BLOCK_BITS"], defs["GP_JPEG_HEAD_BYTES"], defs["GP_JPEG_MAX_BATCH"], defs["GP_JPEG_MAX_SIDE"],
             defs["GP_JPEG_420"], defs["GP_JPEG_444"]) == \
         (JPG.RESTART_MCUS, JPG.BLOCK_BITS, JPG.HEAD_BYTES, JPG.MAX_BATCH, JPG.MAX_SIDE, JPG.SUB_420, JPG.SUB_444)

@@ -13,59 +13,35 @@ import numpy as np
 import pytest
 import torch
 
+import abi_check
 import jpeg_decode_cases as D
 import jpeg_decode_ref as REF
 import jpeg_sync_cases as SC
 from gaussianprediction_amd import _lib, jpeg_decode as JD, jpeg_sync as JS
-from test_jpeg_decode_host import _POINTEES, _SCALARS, _compiler
+from test_jpeg_decode_host import _compiler
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 
-
-def _header():
-    hdr = open(os.path.join(ROOT, "include", "gp_jpeg_sync.h")).read()
-    return re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
+_SCALARS = {"int": C.c_int32, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint32_t": C.c_uint32, "gp_stream_t": _lib.Ptr}
+_POINTEES = {"void", "uint8_t", "uint32_t", "int64_t", "int32_t", "float"}
 
 
 def test_prototype_table_equals_the_header():
-    hdr = re.sub(r"^\s*#.*$", "", _header(), flags=re.M)
-    protos = {}
-    for ret, name, params in re.findall(r"([A-Za-z_][\w\s\*]*?)\b(gp_[a-z_0-9]+)\s*\(([^;{]*?)\)\s*;", hdr):
-        assert name not in protos, name
-        params = " ".join(params.split())
-        plist = [] if params in ("", "void") else [re.sub(r"\s*\w+$", "", p.strip()) for p in params.split(",")]
-        protos[name] = (" ".join(ret.split()), [" ".join(t.replace("const", " ").replace("*", " * ").split()) for t in plist])
-    assert set(protos) == set(JS.PROTOTYPES) and len(protos) == 3
-    for name, (ret, params) in protos.items():
-        restype, argtypes = JS.PROTOTYPES[name]
-        assert restype is {"int": C.c_int32, "int64_t": C.c_int64}[ret], (name, ret, restype)
-        assert len(argtypes) == len(params), (name, params, argtypes)
-        for k, (ctype, cls) in enumerate(zip(params, argtypes)):
-            if "*" in ctype:
-                assert ctype.split("*")[0].strip() in _POINTEES and cls is _lib.Ptr, (name, k, ctype, cls)
-            else:
-                assert cls is _SCALARS[ctype], (name, k, ctype, cls)
+    protos = abi_check.check_table(JS.ABI, 3, _SCALARS, _POINTEES)
+    assert JS.ABI.prototypes is JS.PROTOTYPES and JS.ABI.header == "gp_jpeg_sync.h"
     assert protos["gp_jpeg_sync_decode"][1][-1] == "gp_stream_t"         # the stream is the last parameter
     # gp_jpeg_decode's arguments, and info in front of the scratch
     assert [c for c in JS.PROTOTYPES["gp_jpeg_sync_decode"][1]] == JD.PROTOTYPES["gp_jpeg_decode"][1][:15] + [_lib.Ptr] + JD.PROTOTYPES["gp_jpeg_decode"][1][15:]
-    from gaussianprediction_amd import jpeg_ops, png_decode
-    others = set(_lib.PROTOTYPES) | set(jpeg_ops.PROTOTYPES) | set(png_decode.PROTOTYPES) | set(JD.PROTOTYPES)
-    assert not set(protos) & others                                       # none of the new names leaks into another table
 
 
 def test_symbols_and_constants():
-    defs = {k: int(v) for k, v in re.findall(r"#define (GP_JPEG_SYNC_[A-Z0-9_]+) (\d+)u?\b", _header())}
-    assert defs["GP_JPEG_SYNC_ABI_VERSION"] == JS.GP_JPEG_SYNC_ABI_VERSION == 1
+    defs = {k: int(v) for k, v in re.findall(r"#define (GP_JPEG_SYNC_[A-Z0-9_]+) (\d+)u?\b", abi_check.header_text("gp_jpeg_sync.h"))}
+    assert defs["GP_JPEG_SYNC_ABI_VERSION"] == JS.GP_JPEG_SYNC_ABI_VERSION == JS.ABI.version == 1
     assert (defs["GP_JPEG_SYNC_SUBSEQ_BYTES"], defs["GP_JPEG_SYNC_CHUNK"]) == (JS.S, JS.C)
     codes = {k[len("GP_JPEG_SYNC_"):]: v for k, v in defs.items() if k[len("GP_JPEG_SYNC_"):] not in ("ABI_VERSION", "SUBSEQ_BYTES", "CHUNK")}
     assert codes == {v: k for k, v in JS.STATUS.items()} == {"OK": SC.OK, "SERIAL": SC.SERIAL}
     assert JS.MIN_BYTES >= 2 * JS.S and JS.MIN_BYTES % JS.S == 0
-    l = JS.lib()
-    assert l is _lib.lib() and int(l.gp_jpeg_sync_abi_version()) == 1
-    for name, (restype, argtypes) in JS.PROTOTYPES.items():
-        fn = getattr(l, name)
-        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
+    abi_check.check_applied(JS.ABI)
 
 
 def test_c_entries_refuse_before_they_look_at_a_pointer():

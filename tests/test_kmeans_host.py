@@ -11,6 +11,7 @@ import re
 import pytest
 import torch
 
+import abi_check
 import kmeans_ref as R
 from gaussianprediction_amd import _lib, kmeans_ops as KM
 from gaussianprediction_amd.training import kmeans as training_kmeans
@@ -26,48 +27,17 @@ _SCALARS = {"int": C.c_int32, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint3
 _POINTEES = {"float", "void", "int32_t", "uint32_t"}
 
 
-def _header():
-    hdr = open(os.path.join(ROOT, "include", "gp_kmeans.h")).read()
-    return re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
-
-
-def _header_prototypes():
-    hdr = re.sub(r"typedef struct.*?\}\s*\w+;", "", _header(), flags=re.S)
-    hdr = re.sub(r"^\s*#.*$", "", hdr, flags=re.M)
-    protos = {}
-    for ret, name, params in re.findall(r"([A-Za-z_][\w\s\*]*?)\b(gp_[a-z_0-9]+)\s*\(([^;{]*?)\)\s*;", hdr):
-        assert name not in protos, name
-        params = " ".join(params.split())
-        plist = [] if params in ("", "void") else [re.sub(r"\s*\w+$", "", p.strip()) for p in params.split(",")]
-        protos[name] = (" ".join(ret.split()), [" ".join(t.replace("const", " ").replace("*", " * ").split()) for t in plist])
-    return protos
-
-
 def test_prototype_table_equals_the_header():
-    protos = _header_prototypes()
-    assert set(protos) == set(KM.PROTOTYPES), set(protos) ^ set(KM.PROTOTYPES)
-    assert len(protos) == 5
-    for name, (ret, params) in protos.items():
-        restype, argtypes = KM.PROTOTYPES[name]
-        assert restype is {"int": C.c_int32, "int64_t": C.c_int64}[ret], (name, ret, restype)
-        assert len(argtypes) == len(params), (name, params, argtypes)
-        for k, (ctype, cls) in enumerate(zip(params, argtypes)):
-            if "*" in ctype:
-                assert ctype.split("*")[0].strip() in _POINTEES and cls is _lib.Ptr, (name, k, ctype, cls)
-            else:
-                assert cls is _SCALARS[ctype], (name, k, ctype, cls)
+    protos = abi_check.check_table(KM.ABI, 5, _SCALARS, _POINTEES)
+    assert KM.ABI.prototypes is KM.PROTOTYPES and KM.ABI.header == "gp_kmeans.h"
+    for name, (_, params) in protos.items():
         assert params == [] or params[-1] == "gp_stream_t" or name == "gp_kmeans_scratch_bytes", name      # the stream is the last parameter
-    assert not set(protos) & set(_lib.PROTOTYPES)            # none of them leaks into the main ABI's table
 
 
 def test_symbols_and_constants():
-    defs = {k: int(v) for k, v in re.findall(r"#define (GP_KMEANS_[A-Z0-9_]+) (\d+)u?\b", _header())}
-    assert defs["GP_KMEANS_ABI_VERSION"] == KM.GP_KMEANS_ABI_VERSION == 1
-    l = KM.lib()
-    assert l is _lib.lib() and int(l.gp_kmeans_abi_version()) == 1
-    for name, (restype, argtypes) in KM.PROTOTYPES.items():
-        fn = getattr(l, name)
-        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
+    defs = {k: int(v) for k, v in re.findall(r"#define (GP_KMEANS_[A-Z0-9_]+) (\d+)u?\b", abi_check.header_text("gp_kmeans.h"))}
+    assert defs["GP_KMEANS_ABI_VERSION"] == KM.GP_KMEANS_ABI_VERSION == KM.ABI.version == 1
+    abi_check.check_applied(KM.ABI)
     assert (defs["GP_KMEANS_BLOCK"], defs["GP_KMEANS_MAX_D"], defs["GP_KMEANS_MAX_K"], defs["GP_KMEANS_MAX_ROWS"], defs["GP_KMEANS_MAX_ITERS"]) == \
         (KM.BLOCK, KM.MAX_D, KM.MAX_K, KM.MAX_ROWS, KM.MAX_ITERS) == (256, 64, 4096, 2 ** 31 - 1, 1000)
     assert (defs["GP_KMEANS_STATUS_WORDS"], defs["GP_KMEANS_ST_ITERATIONS"], defs["GP_KMEANS_ST_CONVERGED"], defs["GP_KMEANS_ST_SHIFT2"]) == \

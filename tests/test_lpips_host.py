@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import abi_check
 import lpips_ref as R
 from gaussianprediction_amd import _lib, lpips as L
 
@@ -63,45 +64,15 @@ _SCALARS = {"int": C.c_int32, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint3
 _POINTEES = {"float", "double", "void", "int32_t", "uint32_t"}
 
 
-def _header_prototypes():
-    hdr = open(os.path.join(ROOT, "include", "gp_lpips.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
-    hdr = re.sub(r"^\s*#.*$", "", hdr, flags=re.M)
-    protos = {}
-    for ret, name, params in re.findall(r"([A-Za-z_][\w\s\*]*?)\b(gp_[a-z_0-9]+)\s*\(([^;{]*?)\)\s*;", hdr):
-        assert name not in protos, name
-        params = " ".join(params.split())
-        plist = [] if params in ("", "void") else [re.sub(r"\s*\w+$", "", p.strip()) for p in params.split(",")]
-        protos[name] = (" ".join(ret.split()), [" ".join(t.replace("const", " ").replace("*", " * ").split()) for t in plist])
-    return protos
-
-
 def test_prototype_table_equals_the_header():
-    protos = _header_prototypes()
-    assert set(protos) == set(L.PROTOTYPES), set(protos) ^ set(L.PROTOTYPES)
-    assert len(protos) == 9
-    for name, (ret, params) in protos.items():
-        restype, argtypes = L.PROTOTYPES[name]
-        assert restype is {"int": C.c_int32, "int64_t": C.c_int64}[ret], (name, ret, restype)
-        assert len(argtypes) == len(params), (name, params, argtypes)
-        for k, (ctype, cls) in enumerate(zip(params, argtypes)):
-            if "*" in ctype:
-                assert ctype.split("*")[0].strip() in _POINTEES and cls is _lib.Ptr, (name, k, ctype, cls)
-            else:
-                assert cls is _SCALARS[ctype], (name, k, ctype, cls)
-    # none of them leaks into the main ABI's table
-    assert not set(protos) & set(_lib.PROTOTYPES)
+    abi_check.check_table(L.ABI, 9, _SCALARS, _POINTEES)
+    assert L.ABI.prototypes is L.PROTOTYPES and L.ABI.header == "gp_lpips.h"
 
 
 def test_symbols_are_exported_and_bound():
     hdr = open(os.path.join(ROOT, "include", "gp_lpips.h")).read()
-    assert int(re.search(r"#define GP_LPIPS_ABI_VERSION (\d+)", hdr).group(1)) == L.GP_LPIPS_ABI_VERSION == 1
-    l = L.lib()
-    assert l is _lib.lib()
-    for name, (restype, argtypes) in L.PROTOTYPES.items():
-        fn = getattr(l, name)
-        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
-    assert int(l.gp_lpips_abi_version()) == 1
+    assert int(re.search(r"#define GP_LPIPS_ABI_VERSION (\d+)", hdr).group(1)) == L.GP_LPIPS_ABI_VERSION == L.ABI.version == 1
+    abi_check.check_applied(L.ABI)
     defs = {k: int(v) for k, v in re.findall(r"#define (GP_LPIPS_[A-Z0-9_]+) (\d+)u?\b", hdr)}
     assert (defs["GP_LPIPS_ALEX"], defs["GP_LPIPS_VGG"], defs["GP_LPIPS_SQUEEZE"]) == (L.NETS["alex"], L.NETS["vgg"], L.NETS["squeeze"])
     assert (defs["GP_LPIPS_QUANTIZE8"], defs["GP_LPIPS_TAPS"], defs["GP_LPIPS_COLUMNS"]) == (L.QUANTIZE8, L.TAPS, L.COLUMNS)

@@ -13,58 +13,27 @@ import numpy as np
 import pytest
 import torch
 
+import abi_check
 import png_cases as P
 from gaussianprediction_amd import _lib, eval_render as ER, png_ops as PNG
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 
 # ---- one signature per entry point, two statements of it: include/gp_png.h and png_ops.PROTOTYPES ----
 _SCALARS = {"int": C.c_int32, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint32_t": C.c_uint32, "gp_stream_t": _lib.Ptr}
 _POINTEES = {"void", "uint8_t", "uint32_t"}
 
 
-def _header():
-    hdr = open(os.path.join(ROOT, "include", "gp_png.h")).read()
-    return re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
-
-
-def _header_prototypes():
-    hdr = re.sub(r"^\s*#.*$", "", _header(), flags=re.M)
-    protos = {}
-    for ret, name, params in re.findall(r"([A-Za-z_][\w\s\*]*?)\b(gp_[a-z_0-9]+)\s*\(([^;{]*?)\)\s*;", hdr):
-        assert name not in protos, name
-        params = " ".join(params.split())
-        plist = [] if params in ("", "void") else [re.sub(r"\s*\w+$", "", p.strip()) for p in params.split(",")]
-        protos[name] = (" ".join(ret.split()), [" ".join(t.replace("const", " ").replace("*", " * ").split()) for t in plist])
-    return protos
-
-
 def test_prototype_table_equals_the_header():
-    protos = _header_prototypes()
-    assert set(protos) == set(PNG.PROTOTYPES), set(protos) ^ set(PNG.PROTOTYPES)
-    assert len(protos) == 4
-    for name, (ret, params) in protos.items():
-        restype, argtypes = PNG.PROTOTYPES[name]
-        assert restype is {"int": C.c_int32, "int64_t": C.c_int64}[ret], (name, ret, restype)
-        assert len(argtypes) == len(params), (name, params, argtypes)
-        for k, (ctype, cls) in enumerate(zip(params, argtypes)):
-            if "*" in ctype:
-                assert ctype.split("*")[0].strip() in _POINTEES and cls is _lib.Ptr, (name, k, ctype, cls)
-            else:
-                assert cls is _SCALARS[ctype], (name, k, ctype, cls)
+    protos = abi_check.check_table(PNG.ABI, 4, _SCALARS, _POINTEES)
+    assert PNG.ABI.prototypes is PNG.PROTOTYPES and PNG.ABI.header == "gp_png.h"
     assert protos["gp_png_encode"][1][-1] == "gp_stream_t"         # the stream is the last parameter
-    assert not set(protos) & set(_lib.PROTOTYPES)                  # none of them leaks into the main ABI's table
 
 
 def test_symbols_and_constants():
-    defs = {k: int(v) for k, v in re.findall(r"#define (GP_PNG_[A-Z0-9_]+) (\d+)u?\b", _header())}
-    assert defs["GP_PNG_ABI_VERSION"] == PNG.GP_PNG_ABI_VERSION == 1
-    l = PNG.lib()
-    assert l is _lib.lib() and int(l.gp_png_abi_version()) == 1
-    for name, (restype, argtypes) in PNG.PROTOTYPES.items():
-        fn = getattr(l, name)
-        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
+    defs = {k: int(v) for k, v in re.findall(r"#define (GP_PNG_[A-Z0-9_]+) (\d+)u?\b", abi_check.header_text("gp_png.h"))}
+    assert defs["GP_PNG_ABI_VERSION"] == PNG.GP_PNG_ABI_VERSION == PNG.ABI.version == 1
+    abi_check.check_applied(PNG.ABI)
     assert (defs["GP_PNG_BAND_BYTES"], defs["GP_PNG_MAX_BATCH"], defs["GP_PNG_SRC_F32"], defs["GP_PNG_SRC_U8"], defs["GP_PNG_FILTER_NONE"]) == \
         (PNG.BAND_BYTES, PNG.MAX_BATCH, PNG.SRC_F32, PNG.SRC_U8, PNG.FILTER_NONE)
     assert PNG.BAND_BYTES >= 8192 and PNG.BAND_BYTES % 256 == 0
