@@ -3,7 +3,7 @@ restart interval, dequantisation, the integer inverse DCT, chroma upsampling, th
 division by 255 -- what the loaders did per file with a host library -- and the frames of a Motion-JPEG AVI file.
 
   [REF scene/dataset_readers.py:210-218]   Image.open whatever the dataset holds
-  [REF utils/general_utils.py:21-27]       PILtoTorch: resize, / 255.0, permute
+  [REF utils/general_utils.py:21-27]       PILtoTorch: resize, / 255.0, permute (the resize: `resize=`, through resize_ops)
   [REF metrics.py:148]                     deltas/%05d.jpg
 
 The host walks the markers (`parse`), finds the restart intervals by their RST markers and copies the scans of all files, with
@@ -359,21 +359,31 @@ def _sync_flag(sync):
     return bool(sync)
 
 
-def decode(files, *, device, dtype=torch.uint8, names=None, sync=False, _pool=None):
+def decode(files, *, device, dtype=torch.uint8, names=None, sync=False, resize=None, resample="bicubic", _pool=None):
     """JPEG files held in memory (a list of bytes) -> a list of [3, H, W] R G B tensors on `device`, one per file, in order.
     dtype: torch.uint8, or torch.float32 = byte / 255 (bit-equal to uint8.to(float32) / 255.0).  The files are grouped by shape and
     subsampling; a group is one launch sequence.  The device is read once.  A damaged file raises GpHipError naming the file and the
     status word.
     sync: True or "auto" sends the files without restart markers that jpeg_sync.eligible takes through jpeg_sync.decode_once (many
     lanes per file instead of one); what comes back SERIAL there, and every other file, goes through the one-lane call in a second
-    pass, so the pixels and every error are those of sync=False.  Off by default."""
+    pass, so the pixels and every error are those of sync=False.  Off by default.
+    resize: (width, height), or a callable (w, h) -> (width, height) -- every image is decoded as uint8 and resized as Image.resize
+    does it, byte for byte (resize_ops.resize, filter `resample`), one batched call per shape group; `dtype` applies to the result."""
     _arguments(device, dtype)                                                   # (the device is checked before any file is looked at)
     sync = _sync_flag(sync)
+    out_dtype = dtype
+    if resize is not None:
+        from . import resize_ops
+        resize_ops.filter_id(resample)
+        dtype = torch.uint8
     files = list(files)
     names = [f"<file {i}>" for i in range(len(files))] if names is None else [os.fspath(n) for n in names]
     if len(names) != len(files):
         raise RuntimeError(f"jpeg_decode: {len(files)} files but {len(names)} names")
     items = [f if isinstance(f, SimpleNamespace) else parse(f, n) for f, n in zip(files, names)]
+    if resize is not None:
+        for it in items:
+            resize_ops.target_size(resize, it.W, it.H, it.name)                 # (a target size of 0 names its file, before the device)
     images, rest = [None] * len(items), list(range(len(items)))
     if sync:
         from . import jpeg_sync
@@ -388,10 +398,12 @@ def decode(files, *, device, dtype=torch.uint8, names=None, sync=False, _pool=No
         if s:
             raise _lib.GpHipError(f"jpeg_decode: {items[i].name}: the device decoder reports status {s} (GP_JPEG_DECODE_{STATUS.get(s, '?')})")
         images[i] = im
+    if resize is not None:
+        images = resize_ops.resize_each(images, resize, resample, dtype=out_dtype, names=[it.name for it in items])
     return images
 
 
-def decode_files(paths, *, device, dtype=torch.uint8, sync=False):
+def decode_files(paths, *, device, dtype=torch.uint8, sync=False, resize=None, resample="bicubic"):
     """`decode` of files on disk: at most READER_THREADS threads read and parse them and fill the staging buffer."""
     _arguments(device, dtype)
     _sync_flag(sync)
@@ -403,7 +415,7 @@ def decode_files(paths, *, device, dtype=torch.uint8, sync=False):
 
     with ThreadPoolExecutor(max_workers=max(1, min(READER_THREADS, len(paths)))) as pool:
         items = list(pool.map(load, paths))
-        return decode(items, device=device, dtype=dtype, names=paths, sync=sync, _pool=pool)
+        return decode(items, device=device, dtype=dtype, names=paths, sync=sync, resize=resize, resample=resample, _pool=pool)
 
 
 # ---- Motion-JPEG in AVI ----------------------------------------------------------------------------------------------------------------
@@ -463,12 +475,16 @@ def avi_frames(data, name="<bytes>"):
     return width, abs(height), found["frames"]
 
 
-def decode_avi(path, *, device, dtype=torch.uint8, frames=None, sync=False):
+def decode_avi(path, *, device, dtype=torch.uint8, frames=None, sync=False, resize=None, resample="bicubic"):
     """The frames of a Motion-JPEG AVI file (one MJPG video stream, as jpeg_ops.VideoWriter writes it) as one [F, 3, H, W] tensor on
     `device`.  frames: the frame numbers to decode, in the order wanted (default: all).  AVI_BATCH frames per decode call.  sync: as
-    `decode` -- the frames other encoders write carry no restart markers."""
+    `decode` -- the frames other encoders write carry no restart markers.  resize, resample: as `decode`; the result is then
+    [F, 3, height, width]."""
     device = _arguments(device, dtype)
     _sync_flag(sync)
+    if resize is not None:
+        from . import resize_ops
+        resize_ops.filter_id(resample)
     path = os.fspath(path)
     with open(path, "rb") as fp:
         data = fp.read()
@@ -481,8 +497,10 @@ def decode_avi(path, *, device, dtype=torch.uint8, frames=None, sync=False):
     for it in items:
         if (it.W, it.H) != (width, height):
             raise ValueError(f"jpeg_decode: {it.name}: a frame of {it.H} x {it.W} in a video of {height} x {width}")
+    if resize is not None:
+        width, height = resize_ops.target_size(resize, width, height, path)
     out = torch.empty(len(items), 3, height, width, dtype=dtype, device=device)
     for lo in range(0, len(items), AVI_BATCH):
-        imgs = decode(items[lo:lo + AVI_BATCH], device=device, dtype=dtype, sync=sync)
+        imgs = decode(items[lo:lo + AVI_BATCH], device=device, dtype=dtype, sync=sync, resize=resize, resample=resample)
         out[lo:lo + len(imgs)] = torch.stack(imgs)
     return out

@@ -200,17 +200,25 @@ def report_views(model, cameras, gts, pipe, bg, iteration, *, speculative=True, 
     return {"L1": float(m[L1]), "PSNR": float(m[PSNR_CH]), "per_view": table}
 
 
-def _load_rgb(path, device):
-    """An image file as `to_tensor` gives it: [1,3,H,W] float32 = byte / 255 (true division), first three channels."""
+def _load_rgb(path, device, resize=None):
+    """An image file as `to_tensor` gives it: [1,3,H,W] float32 = byte / 255 (true division), first three channels.  resize (a
+    callable (w, h) -> (width, height)): the decoded bytes, all channels, go up and are resized on the device as Image.resize does
+    it (resize_ops.resize), before the slice -- the order of the reference's readImages."""
     from PIL import Image       # (lazy: only the directory form needs it)
     import numpy as np
     arr = np.array(Image.open(path))
     if arr.ndim == 2:
         arr = arr[:, :, None]
-    t = torch.from_numpy(arr).permute(2, 0, 1)[:3]
+    t = torch.from_numpy(arr).permute(2, 0, 1)
     if t.dtype != torch.uint8:
         raise RuntimeError(f"evaluate_dirs: {path} is not an 8-bit image")
-    return (t.to(torch.float32) / 255.0)[None].contiguous().to(device)
+    if resize is not None:
+        from . import resize_ops
+        if t.shape[0] not in (1, 3, 4):
+            raise RuntimeError(f"evaluate_dirs: {path} has {t.shape[0]} channels: L, RGB and RGBA images are resized on the device")
+        size = resize_ops.target_size(resize, t.shape[2], t.shape[1], path)
+        return resize_ops.resize(t.contiguous().to(device), size, dtype=torch.float32)[None, :3].contiguous()
+    return (t[:3].to(torch.float32) / 255.0)[None].contiguous().to(device)
 
 
 def _lpips_from(weights, device):
@@ -222,7 +230,7 @@ def _lpips_from(weights, device):
     return [_lp.cached(net, device, os.fspath(weights)) for net in ("vgg", "alex")]
 
 
-def _decode_by_signature(paths, device, sync=False):
+def _decode_by_signature(paths, device, sync=False, resize=None):
     """evaluate_dirs' device_decode: every file goes by its first bytes to png_decode or jpeg_decode (float32, the first three
     channels); one call of each per group.  Anything else raises, naming the file: there is no host decoder behind this path."""
     from . import jpeg_decode, png_decode
@@ -244,15 +252,16 @@ def _decode_by_signature(paths, device, sync=False):
             continue
         names = [paths[i] for i in idx]
         if kind == "png":
-            imgs = png_decode.decode(files, device=device, dtype=torch.float32, channels=3, names=names)
+            imgs = png_decode.decode(files, device=device, dtype=torch.float32, channels=3, names=names, resize=resize)
         else:
-            imgs = jpeg_decode.decode(files, device=device, dtype=torch.float32, names=names, sync=sync)
+            imgs = jpeg_decode.decode(files, device=device, dtype=torch.float32, names=names, sync=sync, resize=resize)
         for i, im in zip(idx, imgs):
             out[i] = im
     return out
 
 
-def _score_decoded_groups(rdir, gdir, rnames, gnames, mdir, device, table, nets, ltabs, write, jw, pending, group, by_signature=False, sync=False):
+def _score_decoded_groups(rdir, gdir, rnames, gnames, mdir, device, table, nets, ltabs, write, jw, pending, group, by_signature=False, sync=False,
+                          resize=None):
     """evaluate_dirs' loop with device_png: `group` pairs per png_decode.decode_files call (float32, the first three channels), and
     one batched image_metrics call per run of pairs of one shape.  by_signature (device_decode): PNG and JPEG files, each to its
     decoder."""
@@ -260,7 +269,8 @@ def _score_decoded_groups(rdir, gdir, rnames, gnames, mdir, device, table, nets,
     for lo in range(0, len(rnames), group):
         hi = min(len(rnames), lo + group)
         paths = [os.path.join(rdir, n) for n in rnames[lo:hi]] + [os.path.join(gdir, n) for n in gnames[lo:hi]]
-        imgs = _decode_by_signature(paths, device, sync) if by_signature else png_decode.decode_files(paths, device=device, dtype=torch.float32, channels=3)
+        imgs = _decode_by_signature(paths, device, sync, resize) if by_signature else \
+            png_decode.decode_files(paths, device=device, dtype=torch.float32, channels=3, resize=resize)
         renders, gts = imgs[:hi - lo], imgs[hi - lo:]
         i = lo
         while i < hi:
@@ -279,7 +289,8 @@ def _score_decoded_groups(rdir, gdir, rnames, gnames, mdir, device, table, nets,
             i = j
 
 
-def evaluate_dirs(path, device="cuda", write=True, lpips_weights=None, device_jpeg=False, device_png=False, png_group=16, device_decode=False, decode_sync=False):
+def evaluate_dirs(path, device="cuda", write=True, lpips_weights=None, device_jpeg=False, device_png=False, png_group=16, device_decode=False, decode_sync=False,
+                  resize=False, resize_ratio=0.5):
     """The directory form of the reference's metrics.py [REF metrics.py:113-178]: for every `<path>/<method>/` holding `renders/`
     and `gt/`, score the sorted image pairs (files whose name contains "depth" are skipped), write `<method>/deltas/%05d.jpg` and
     -- as the reference does -- `<path>/results.json` and `<path>/per_view.json` of the last method.  Keys: SSIM, PSNR, MS-SSIM,
@@ -294,10 +305,17 @@ def evaluate_dirs(path, device="cuda", write=True, lpips_weights=None, device_jp
     4:2:0) -- a gt directory of .jpg frames, or .jpg renders; the numbers are the default path's.  Off by default.
     decode_sync: with device_decode, jpeg_decode.decode's `sync` -- JPEG files without restart markers go through jpeg_sync's many
     lanes; the pixels, and so the numbers, are the same.  Off by default.
+    resize, resize_ratio: the reference's options of the same names [REF metrics.py evaluate, readImages] -- with resize=True every
+    render and ground-truth image is resized to (int(w * resize_ratio), int(h * resize_ratio)) with Pillow's bicubic filter before it
+    is scored, on the device and byte for byte as Image.resize does it (resize_ops): the default path uploads the decoded bytes and
+    resizes them there, device_png / device_decode pass `resize=` to the decoders.  The numbers are those of scoring files that
+    Pillow resized.  A target size of 0 raises, naming the file.  With resize=False the ratio is ignored.
     Returns {method: {"summary": ..., "per_view": ...}} with the dictionaries that were written."""
     from PIL import Image
     device = torch.device(device)
     nets = _lpips_from(lpips_weights, device) if lpips_weights is not None else []
+    ratio = float(resize_ratio)
+    target = (lambda w, h: (int(w * ratio), int(h * ratio))) if resize else None
     result = {}
     for method in sorted(os.listdir(path)):
         mdir = os.path.join(path, method)
@@ -320,7 +338,7 @@ def evaluate_dirs(path, device="cuda", write=True, lpips_weights=None, device_jp
         for i, (rn, gn) in enumerate(zip(rnames, gnames)):
             if device_png or device_decode:
                 break                           # (scored in groups below)
-            render, gt = _load_rgb(os.path.join(rdir, rn), device), _load_rgb(os.path.join(gdir, gn), device)
+            render, gt = _load_rgb(os.path.join(rdir, rn), device, target), _load_rgb(os.path.join(gdir, gn), device, target)
             r = image_metrics(render, gt, out=table[i:i + 1], deltas=write)
             for net, lt in zip(nets, ltabs):
                 net(render, gt, out=lt[i:i + 1])
@@ -330,7 +348,7 @@ def evaluate_dirs(path, device="cuda", write=True, lpips_weights=None, device_jp
                 pending.append(r.deltas)
         if device_png or device_decode:
             _score_decoded_groups(rdir, gdir, rnames, gnames, mdir, device, table, nets, ltabs, write, jw, pending, max(1, int(png_group)),
-                                  by_signature=bool(device_decode), sync=decode_sync)
+                                  by_signature=bool(device_decode), sync=decode_sync, resize=target)
         h = table.cpu() if not nets else torch.cat([table] + [lt[:, :1] for lt in ltabs], dim=1).cpu()      # (one read either way)
         for i, d in enumerate(pending):
             Image.fromarray(d[0].cpu().numpy()).save(os.path.join(mdir, "deltas", "{0:05d}.jpg".format(i)))

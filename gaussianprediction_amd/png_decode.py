@@ -3,7 +3,7 @@ the planar conversion with its division by 255 and, for RGBA ground truth, the c
 file with a host library.
 
   [REF scene/dataset_readers.py:210-218]   Image.open, convert("RGBA"), the composite in numpy
-  [REF utils/general_utils.py:21-27]       PILtoTorch: resize, / 255.0, permute
+  [REF utils/general_utils.py:21-27]       PILtoTorch: resize, / 255.0, permute (the resize: `resize=`, through resize_ops)
 
 The host walks the chunks (`parse`: signature, lengths, every CRC-32, IHDR) and copies the IDAT data of all files, with their segment
 tables, into ONE pinned buffer that goes up in one copy.  A file with exactly ceil(S / 16384) IDAT chunks (S = H (1 + C W)) -- every
@@ -251,21 +251,36 @@ def decode_once(items, banded, *, device, dtype=torch.uint8, channels=None, back
     return images, status, modes, slots
 
 
-def decode(files, *, device, dtype=torch.uint8, channels=None, background=None, names=None, return_modes=False, _pool=None):
+def decode(files, *, device, dtype=torch.uint8, channels=None, background=None, names=None, return_modes=False, resize=None, resample="bicubic",
+           _pool=None):
     """PNG files held in memory (a list of bytes) -> a list of [C_out, H, W] tensors on `device`, one per file, in order.
     dtype: torch.uint8, or torch.float32 = byte / 255 (bit-equal to uint8.to(float32) / 255.0).  channels: keep the first `channels`
     channels, as the slice [:channels] would (default: all).  background: three floats on the device -- RGBA files are composited over it to three channels as the
     D-NeRF reader does [REF scene/dataset_readers.py:212-218].  The files are grouped by shape; a group is one launch sequence.  The
     device is read once, and once more only if a file that looked banded was not (those are decoded again as one stream).  A
     damaged file raises GpHipError naming the file and the status word.  return_modes: also the final mode per file
-    (MODE_BANDED / MODE_SERIAL)."""
+    (MODE_BANDED / MODE_SERIAL).
+    resize: (width, height), or a callable (w, h) -> (width, height) -- every image is resized as Image.resize does it, byte for byte
+    (resize_ops.resize, filter `resample`): a shape group is decoded as uint8 with all of the file's channels, an RGBA file's alpha
+    plane among them, and resized in one batched call; `channels` and `background` apply to the resized image, as [:3] follows
+    .resize in the reference [REF metrics.py readImages], and `dtype` last."""
     _arguments(device, dtype, background)                                       # (the device is checked before any file is looked at)
+    if resize is not None:
+        from . import resize_ops
+        resize_ops.filter_id(resample)
     files = list(files)
     names = [f"<file {i}>" for i in range(len(files))] if names is None else [os.fspath(n) for n in names]
     if len(names) != len(files):
         raise RuntimeError(f"png_decode: {len(files)} files but {len(names)} names")
     items = [f if isinstance(f, SimpleNamespace) else parse(f, n) for f, n in zip(files, names)]
     kw = dict(device=device, dtype=dtype, channels=channels, background=background, pool=_pool)
+    if resize is not None:
+        groups(items, channels, background)                                     # (what channels and background ask of the files, before the device)
+        for it in items:
+            if it.C == 2:
+                raise ValueError(f"png_decode: {it.name}: grey + alpha images are not resized on the device")
+            resize_ops.target_size(resize, it.W, it.H, it.name)
+        kw.update(dtype=torch.uint8, channels=None, background=None)
     banded = [it.banded for it in items]
     images, status, modes, _ = decode_once(items, banded, **kw)
     again = [i for i, s in enumerate(status) if s == NOT_BANDED and banded[i]]
@@ -276,10 +291,33 @@ def decode(files, *, device, dtype=torch.uint8, channels=None, background=None, 
     for it, s in zip(items, status):
         if s:
             raise _lib.GpHipError(f"png_decode: {it.name}: the device decoder reports status {s} (GP_PNG_DECODE_{STATUS.get(s, '?')})")
+    if resize is not None:
+        images = _resized(images, items, resize, resample, dtype, channels, _arguments(device, dtype, background)[1])
     return (images, modes) if return_modes else images
 
 
-def decode_files(paths, *, device, dtype=torch.uint8, channels=None, background=None, return_modes=False):
+def _resized(images, items, size, resample, dtype, channels, background):
+    """decode's resize=: the decoded uint8 images, all channels, through resize_ops.resize_each; then the channel slice, or the
+    composite over `background` -- the D-NeRF reader's formula in float64, as gp_png_decode computes it on full-size images -- and
+    the conversion to `dtype`."""
+    from . import resize_ops
+    names = [it.name for it in items]
+    if background is None:
+        out = resize_ops.resize_each(images, size, resample, dtype=dtype, names=names)
+        return out if channels is None else [im[:int(channels)] for im in out]
+    bg = background.to(torch.float64).view(3, 1, 1)
+    full = torch.full((), 255.0, dtype=torch.float64, device=bg.device)       # (a tensor: torch divides by a Python scalar with a reciprocal)
+    out = []
+    for im in resize_ops.resize_each(images, size, resample, names=names):
+        norm = im.to(torch.float64) / full
+        arr = norm[:3] * norm[3:4] + bg * (1.0 - norm[3:4])
+        byte = ((arr * full).trunc().to(torch.int64) & 255).to(torch.uint8)
+        # (float32 = byte / 255 by the copy path of gp_resize_u8: one correctly rounded division)
+        out.append(byte if dtype == torch.uint8 else resize_ops.resize(byte, (byte.shape[2], byte.shape[1]), dtype=torch.float32))
+    return out
+
+
+def decode_files(paths, *, device, dtype=torch.uint8, channels=None, background=None, return_modes=False, resize=None, resample="bicubic"):
     """`decode` of files on disk: at most READER_THREADS threads read and parse them and fill the staging buffer."""
     _arguments(device, dtype, background)
     paths = [os.fspath(p) for p in paths]
@@ -291,4 +329,4 @@ def decode_files(paths, *, device, dtype=torch.uint8, channels=None, background=
     with ThreadPoolExecutor(max_workers=max(1, min(READER_THREADS, len(paths)))) as pool:
         items = list(pool.map(load, paths))
         return decode(items, device=device, dtype=dtype, channels=channels, background=background, names=paths,
-                      return_modes=return_modes, _pool=pool)
+                      return_modes=return_modes, resize=resize, resample=resample, _pool=pool)
