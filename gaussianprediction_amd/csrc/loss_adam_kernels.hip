@@ -236,7 +236,13 @@ __global__ __launch_bounds__(256) void gp_l1_ssim_bwd_kernel(const float* __rest
 // read them back with a halo: ~370 MB of traffic at 1352 x 1014 for 16 MB of images).  Same filter chains in the same order: the
 // gradient and the per-tile sums are bit-identical to gp_l1_ssim_fwd_kernel + gp_l1_ssim_bwd_kernel.
 // LDS: the image halos (22 KB; the derivative maps take their place once the last horizontal pass has read them) + two horizontally
-// filtered planes at a time (18 KB; later the backward's three) = 40 KB, three to four workgroups per CU.
+// filtered planes at a time (18 KB; later the backward's three) = 39 952 B, four workgroups per CU (98 VGPRs allow five; the LDS does not).
+// Shape: a workgroup stays ONE 32 x 32 accounting tile.  Workgroups of 64 x 32, 32 x 64 and 64 x 64 outputs (512 / 1 024 threads, a 256-
+// thread group per accounting tile in the last phase) redo less of the halo per output and were each slower all the same: two or one
+// workgroup per CU leave nothing to run beside a barrier, and 1 056 workgroups of 64 x 64 are 4.1 rounds over 256 CUs
+// (profiles/loss_tiles_ab.txt).  What the kernel waited for was its LDS and its staging: every horizontal filter item sits on the lane
+// next to the item of the NEXT ROW (not of the same row), the window reads stay single 8-byte reads, and a workgroup whose staged
+// rectangle lies inside the image stages whole rows with scalar addressing.
 // ------------------------------------------------------------------------------------------------
 #define LF (LT + 4 * LH)    // staged image edge (52)
 #define LFP (LF + 1)
@@ -256,6 +262,10 @@ __global__ __launch_bounds__(256) void gp_l1_ssim_fused_kernel(const float* __re
     f2 (*s_g01)[LHP] = (f2 (*)[LHP]) & s_h[0][0];
     float (*s_g2)[LHP] = (float (*)[LHP])((float*)&s_h[0][0] + 2 * LE * LHP);
     static_assert(3 * LE * LP <= 2 * LF * LFP && 3 * LE * LHP <= 2 * LF * LP, "aliased planes must fit");
+    // A filter window's pairs are read ONE 8-byte read each (volatile: the compiler may not merge two of them into a two-address read,
+    // which the LDS serves at half the bytes per clock; measured 58.6 -> 56.7 us).  The LDS address space is named because a volatile
+    // access through a generic pointer would become a flat load.
+#define LD2(p) (*(const volatile __attribute__((address_space(3))) f2*)(p))
     const int tid = threadIdx.x;
     // The grid is LINEAR (workgroups are dispatched in blockIdx.x order): with a prologue on board (pro.order, gp_train_step_run) workgroup 0
     // orders the composite backward's tiles -- a ~9 us chain of dependent steps that must start first, not behind the last tile -- and
@@ -284,7 +294,28 @@ __global__ __launch_bounds__(256) void gp_l1_ssim_fused_kernel(const float* __re
     const size_t HW = (size_t)H * W;
     const float* a_img = img + ch * HW;
     const float* b_img = gt + ch * HW;
-    {   // halo staging, every load in flight before the first LDS store
+    const int sx0 = tx0 - 2 * LH, sy0 = ty0 - 2 * LH;
+    if (sx0 >= 0 && sy0 >= 0 && sx0 + LF <= W && sy0 + LF <= H) {
+        // halo staging, interior workgroups (one workgroup-uniform branch; almost every workgroup of a real image): the staged
+        // rectangle lies inside the image, so nothing is checked per element.  A wave takes every fourth row, a lane one column: the
+        // row's address is a scalar base plus the lane's offset and the LDS address a constant offset from the first row's -- no vector
+        // arithmetic per load (the element-indexed form below spends some 30 vector instructions per pair of loads on indices and bounds).
+        static_assert(LF % 4 == 0 && LF <= 64, "a wave stages whole rows, every fourth one");
+        const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+        const unsigned lx = (unsigned)min(lane, LF - 1);
+        const float* a0 = a_img + (size_t)(sy0 + wv) * W + sx0;
+        const float* b0 = b_img + (size_t)(sy0 + wv) * W + sx0;
+        float va[LF / 4], vb[LF / 4];
+#pragma unroll
+        for (int u = 0; u < LF / 4; ++u) {
+            const unsigned o = (unsigned)(16 * u) * (unsigned)W + 4u * lx;      // in bytes (32 bits: at most 51 rows past the base)
+            va[u] = *(const float*)((const char*)a0 + o); vb[u] = *(const float*)((const char*)b0 + o);
+        }
+        if (lane < LF) {
+#pragma unroll
+            for (int u = 0; u < LF / 4; ++u) s_ab[wv + 4 * u][lane] = f2{va[u], vb[u]};
+        }
+    } else {   // halo staging at the image's edges, every load in flight before the first LDS store
         constexpr int NST = (LF * LF + 255) / 256;
         float va[NST], vb[NST];
 #pragma unroll
@@ -321,10 +352,13 @@ __global__ __launch_bounds__(256) void gp_l1_ssim_fused_kernel(const float* __re
 #pragma unroll
     for (int round = 0; round < 2; ++round) {
         if (tid < LF * 4) {
-            const int y = tid >> 2, x0 = (tid & 3) * 11;
+            // rows run fastest over the lanes: with the odd row strides a lane group's reads and writes spread over all banks (four
+            // items of one row on neighbouring lanes sit 11 pairs apart and 53 + 11 = 64, 2 * (43 - 11) = 64: up to four lanes on one
+            // bank; SQ_LDS_BANK_CONFLICT 12.2 M -> 2.7 M cycles per launch, 68 -> 60 us)
+            const int y = tid % LF, x0 = (tid / LF) * 11;
             f2 v[21];           // (columns beyond the staged 52 feed outputs beyond 42 only: discarded)
 #pragma unroll
-            for (int j = 0; j < 21; ++j) v[j] = s_ab[y][x0 + j];
+            for (int j = 0; j < 21; ++j) v[j] = LD2(&s_ab[y][x0 + j]);
             if (round == 1) {
 #pragma unroll
                 for (int j = 0; j < 21; ++j) {
@@ -344,7 +378,7 @@ __global__ __launch_bounds__(256) void gp_l1_ssim_fused_kernel(const float* __re
         if (vert) {
             f2 v[17];
 #pragma unroll
-            for (int j = 0; j < 17; ++j) v[j] = s_h[vy0 + j][vx];
+            for (int j = 0; j < 17; ++j) v[j] = LD2(&s_h[vy0 + j][vx]);
 #pragma unroll
             for (int e = 0; e < 7; ++e) {
                 f2 acc = {0.f, 0.f};
@@ -384,11 +418,11 @@ __global__ __launch_bounds__(256) void gp_l1_ssim_fused_kernel(const float* __re
     __syncthreads();
     // ---- the gradient's two filter passes (as gp_l1_ssim_bwd_kernel; maps 0 and 1 as a packed pair)
     if (tid < LE * 4) {
-        const int y = tid >> 2, x0 = (tid & 3) * 8;
+        const int y = tid % LE, x0 = (tid / LE) * 8;        // (rows fastest over the lanes, as in the statistics)
         f2 v[18];
         float v2[18];
 #pragma unroll
-        for (int j = 0; j < 18; ++j) { v[j] = s_m01[y][x0 + j]; v2[j] = s_m2[y][x0 + j]; }
+        for (int j = 0; j < 18; ++j) { v[j] = LD2(&s_m01[y][x0 + j]); v2[j] = s_m2[y][x0 + j]; }
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             f2 acc = {0.f, 0.f};
@@ -408,7 +442,7 @@ __global__ __launch_bounds__(256) void gp_l1_ssim_fused_kernel(const float* __re
             f2 v[14];
             float v2[14];
 #pragma unroll
-            for (int j = 0; j < 14; ++j) { v[j] = s_g01[oy0 + j][ox]; v2[j] = s_g2[oy0 + j][ox]; }
+            for (int j = 0; j < 14; ++j) { v[j] = LD2(&s_g01[oy0 + j][ox]); v2[j] = s_g2[oy0 + j][ox]; }
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 f2 acc = {0.f, 0.f};
@@ -437,6 +471,7 @@ __global__ __launch_bounds__(256) void gp_l1_ssim_fused_kernel(const float* __re
         sums[2 * lb] = (double)l1_tot;
         sums[2 * lb + 1] = (double)ss_tot;
     }
+#undef LD2
 }
 
 // ------------------------------------------------------------------------------------------------
