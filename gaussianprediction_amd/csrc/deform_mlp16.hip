@@ -528,28 +528,33 @@ __device__ __forceinline__ void gemm16s(const _Float16* cur, const _Float16* __r
 }
 
 #include "deform_mlp16_kloop.inc"
-// The split product of a 64-row workgroup as ONE hand-scheduled asm statement per layer (tools/gen_mlp16_kloop.py; same arithmetic and
-// the same MFMA order per accumulator as gemm16s<true, 2>: bit-identical results): weight fragments three k-steps ahead, activation
-// fragments one k-step ahead, counted waits, and -- in the training / backward forms -- the stores of the tile being read: the saved
-// tensor of the previous layer, `st` = this workgroup's [4 row blocks][512 features][16 rows] block, one 1 KB store per k-step (wave w
-// owns row block w; k-step g = features 32 g .. 32 g + 31 of [hi | lo']), so that the stores leave the CU at the rate of the product
-// instead of as a 64 KB burst between two products.  `sel` picks the statement's second path: the layer with its own depth
-// (forward: layer 0, K = 112; data backward: the output layer, K = 16), which carries nothing.
-struct Kloop16sAddr {
+// The product of one layer as ONE hand-scheduled asm statement (tools/gen_mlp16_kloop.py: one emitter, the two forms described by a
+// table; same arithmetic and the same MFMA order per accumulator as the compiler-scheduled gemm16s<true, 2> / gemm16: bit-identical
+// results): weight fragments several k-steps ahead, activation fragments one k-step ahead, counted waits, and -- in the training /
+// backward statements -- the stores of the tile being read: the saved tensor of the previous layer, one 1 KB store per k-step, so that
+// the stores leave the CU at the rate of the product instead of as a 64 KB burst between two products.  `sel` picks the statement's
+// second path: the layer with its own depth (forward: layer 0, K = 112; data backward: the output layer, K = 16), which carries nothing.
+//   split fp16 (M16S_*), 64-row workgroups: weights three k-steps ahead; `st` = this workgroup's [4 row blocks][512 features][16 rows]
+//     block, wave w owns row block w, k-step g = features 32 g .. 32 g + 31 of [hi | lo'].
+//   plain 16-bit (M16P_*(mnemonic): fp16 / bf16 operands), 128-row workgroups, 4 row tiles x 2 feature tiles per wave: weights five
+//     k-steps ahead; wave w owns row blocks 2 w and 2 w + 1, k-step g = features 32 (g & 7) .. + 31 of block 2 w + (g >> 3).
+struct Kloop16Addr {
     uint32_t abase, voff, sbt, vost;
 };
-__device__ __forceinline__ Kloop16sAddr kloop16s_addr(const _Float16* cur, int wave, int lane) {
-    Kloop16sAddr a;
+// W = the row stride of the tile in elements (SP_W / M16_W), WAVE_ROWS = the rows of the tile whose stores one wave carries (16 / 32)
+template <int W, int WAVE_ROWS>
+__device__ __forceinline__ Kloop16Addr kloop16_addr(const void* cur, int wave, int lane) {
+    Kloop16Addr a;
     const int half = lane >> 5, j = lane & 31;
     const uint32_t base = (uint32_t)(uintptr_t)cur;
-    a.abase = base + j * (SP_W * 2) + 2 * ((((j & 15) << 3)) ^ (8 * half));
+    a.abase = base + j * (W * 2) + 2 * ((((j & 15) << 3)) ^ (8 * half));
     a.voff = lane * 16;
-    // the carried store (one 16-row block x 32 features per k-step g, wave w = row block w): 16-lane group G covers features
-    // 32 g + 16 (G & 1) + 0..15 of rows 8 (G >> 1) + 0..7; as a SOURCE of the transpose read lane 4 jj + q of the group supplies the
-    // address of features 4 q .. 4 q + 3 of row jj (+ 4 in the second pass); k-step and pass enter as one XOR with 64 (g ^ pass)
-    // (+ 4096 for the pass), see tools/gen_mlp16_kloop.py
+    // the carried store (one 16-row block x 32 features per k-step g): 16-lane group G covers features 32 g + 16 (G & 1) + 0..15 of
+    // rows 8 (G >> 1) + 0..7; as a SOURCE of the transpose read lane 4 jj + q of the group supplies the address of features
+    // 4 q .. 4 q + 3 of row jj (+ 4 in the second pass); k-step and pass enter as one XOR literal and one offset per form, see the
+    // Form table of tools/gen_mlp16_kloop.py
     const int G = lane >> 4, fb = G & 1, h = G >> 1, jj = (lane >> 2) & 3, q = lane & 3;
-    a.sbt = base + (16 * wave + 8 * h + jj) * (SP_W * 2) + 2 * (((4 * q + 16 * fb) ^ (jj << 3)) + (h << 6));
+    a.sbt = base + (WAVE_ROWS * wave + 8 * h + jj) * (W * 2) + 2 * (((4 * q + 16 * fb) ^ (jj << 3)) + (h << 6));
     a.vost = (16 * fb + (lane & 15)) * 32 + 16 * h;
     return a;
 }
@@ -564,7 +569,7 @@ __device__ __forceinline__ P* uniform_ptr(P* p) {       // a wave-uniform pointe
         [ax11] "=&v"(ax[1][1])
 // forward: am[0][*] hold the biases on entry (the statement never initialises an accumulator with moves), everything else is output only
 template <bool TRAIN>
-__device__ __forceinline__ void kloop16s_fwd(const Kloop16sAddr& a, const _Float16* wh, const _Float16* wl, _Float16* st, int first,
+__device__ __forceinline__ void kloop16s_fwd(const Kloop16Addr& a, const _Float16* wh, const _Float16* wl, _Float16* st, int first,
                                              f32x16 (&am)[2][2], f32x16 (&ax)[2][2]) {
     wh = uniform_ptr(wh); wl = uniform_ptr(wl);
     first = __builtin_amdgcn_readfirstlane(first);
@@ -583,7 +588,7 @@ __device__ __forceinline__ void kloop16s_fwd(const Kloop16sAddr& a, const _Float
     }
 }
 // data backward: nothing is read on entry
-__device__ __forceinline__ void kloop16s_bwd(const Kloop16sAddr& a, const _Float16* wh, const _Float16* wl, _Float16* st, int last,
+__device__ __forceinline__ void kloop16s_bwd(const Kloop16Addr& a, const _Float16* wh, const _Float16* wl, _Float16* st, int last,
                                              f32x16 (&am)[2][2], f32x16 (&ax)[2][2]) {
     wh = uniform_ptr(wh); wl = uniform_ptr(wl); st = uniform_ptr(st);
     last = __builtin_amdgcn_readfirstlane(last);
@@ -594,46 +599,39 @@ __device__ __forceinline__ void kloop16s_bwd(const Kloop16sAddr& a, const _Float
                  : "memory", "scc", M16S_KLOOP_CLOBBERS);
 }
 
-// The plain 16-bit statements (fp16 / bf16 operands, 128-row workgroups: 4 row tiles x 2 feature tiles per wave; tools/gen_mlp16_kloop.py
-// gen_plain): same structure -- two paths, counted waits, weight fragments five k-steps ahead, the carried store (wave w owns row blocks
-// 2 w and 2 w + 1 of the tile, k-step g = features 32 (g & 7) .. + 31 of block 2 w + (g >> 3)).
-__device__ __forceinline__ Kloop16sAddr kloop16p_addr(const void* cur, int wave, int lane) {
-    Kloop16sAddr a;
-    const int half = lane >> 5, j = lane & 31;
-    const uint32_t base = (uint32_t)(uintptr_t)cur;
-    a.abase = base + j * (M16_W * 2) + 2 * ((((j & 15) << 3)) ^ (8 * half));
-    a.voff = lane * 16;
-    const int G = lane >> 4, fb = G & 1, h = G >> 1, jj = (lane >> 2) & 3, q = lane & 3;
-    a.sbt = base + (32 * wave + 8 * h + jj) * (M16_W * 2) + 2 * (((4 * q + 16 * fb) ^ (jj << 3)) + (h << 6));
-    a.vost = (16 * fb + (lane & 15)) * 32 + 16 * h;
-    return a;
-}
 #define M16P_ACC_OUT(c)                                                                                                              \
     [c10] "=&v"(c[1][0]), [c11] "=&v"(c[1][1]), [c20] "=&v"(c[2][0]), [c21] "=&v"(c[2][1]), [c30] "=&v"(c[3][0]), [c31] "=&v"(c[3][1])
 #define M16P_IN(a) [abase] "v"(a.abase), [voff] "v"(a.voff), [swh] "s"(w), [sel] "s"(sel)
 #define M16P_IN_CARRY(a) M16P_IN(a), [sst] "s"(st), [sbt] "v"(a.sbt), [vost] "v"(a.vost)
+// one plain statement STMT for the operand type T; C0 = the constraint of c[0][*] ("+v": they hold the biases on entry, "=&v": nothing
+// is read on entry), IN = the input operands
+#define M16P_KLOOP(STMT, C0, IN)                                                                                                     \
+    do {                                                                                                                             \
+        if constexpr (sizeof(T) == 2 && UsesScale<T>::v)                                                                             \
+            asm volatile(STMT("v_mfma_f32_32x32x16_f16") : [c00] C0(c[0][0]), [c01] C0(c[0][1]), M16P_ACC_OUT(c) : IN                \
+                         : "memory", "scc", M16P_KLOOP_CLOBBERS);                                                                    \
+        else                                                                                                                         \
+            asm volatile(STMT("v_mfma_f32_32x32x16_bf16") : [c00] C0(c[0][0]), [c01] C0(c[0][1]), M16P_ACC_OUT(c) : IN               \
+                         : "memory", "scc", M16P_KLOOP_CLOBBERS);                                                                    \
+    } while (0)
 template <typename T, bool TRAIN>
-__device__ __forceinline__ void kloop16p_fwd(const Kloop16sAddr& a, const T* w, T* st, int sel, f32x16 (&c)[4][2]) {
+__device__ __forceinline__ void kloop16p_fwd(const Kloop16Addr& a, const T* w, T* st, int sel, f32x16 (&c)[4][2]) {
     w = uniform_ptr(w);
     sel = __builtin_amdgcn_readfirstlane(sel);
-    constexpr bool F16 = sizeof(T) == 2 && UsesScale<T>::v;
     if constexpr (TRAIN) {
         st = uniform_ptr(st);
-        if constexpr (F16) asm volatile(M16P_F16_FWD_TRAIN_ASM : [c00] "+v"(c[0][0]), [c01] "+v"(c[0][1]), M16P_ACC_OUT(c) : M16P_IN_CARRY(a) : "memory", "scc", M16P_KLOOP_CLOBBERS);
-        else asm volatile(M16P_BF16_FWD_TRAIN_ASM : [c00] "+v"(c[0][0]), [c01] "+v"(c[0][1]), M16P_ACC_OUT(c) : M16P_IN_CARRY(a) : "memory", "scc", M16P_KLOOP_CLOBBERS);
+        M16P_KLOOP(M16P_FWD_TRAIN_ASM, "+v", M16P_IN_CARRY(a));
     } else {
-        if constexpr (F16) asm volatile(M16P_F16_FWD_INFER_ASM : [c00] "+v"(c[0][0]), [c01] "+v"(c[0][1]), M16P_ACC_OUT(c) : M16P_IN(a) : "memory", "scc", M16P_KLOOP_CLOBBERS);
-        else asm volatile(M16P_BF16_FWD_INFER_ASM : [c00] "+v"(c[0][0]), [c01] "+v"(c[0][1]), M16P_ACC_OUT(c) : M16P_IN(a) : "memory", "scc", M16P_KLOOP_CLOBBERS);
+        M16P_KLOOP(M16P_FWD_INFER_ASM, "+v", M16P_IN(a));
     }
 }
 template <typename T>
-__device__ __forceinline__ void kloop16p_bwd(const Kloop16sAddr& a, const T* w, T* st, int sel, f32x16 (&c)[4][2]) {
+__device__ __forceinline__ void kloop16p_bwd(const Kloop16Addr& a, const T* w, T* st, int sel, f32x16 (&c)[4][2]) {
     w = uniform_ptr(w); st = uniform_ptr(st);
     sel = __builtin_amdgcn_readfirstlane(sel);
-    constexpr bool F16 = sizeof(T) == 2 && UsesScale<T>::v;
-    if constexpr (F16) asm volatile(M16P_F16_BWD_DATA_ASM : [c00] "=&v"(c[0][0]), [c01] "=&v"(c[0][1]), M16P_ACC_OUT(c) : M16P_IN_CARRY(a) : "memory", "scc", M16P_KLOOP_CLOBBERS);
-    else asm volatile(M16P_BF16_BWD_DATA_ASM : [c00] "=&v"(c[0][0]), [c01] "=&v"(c[0][1]), M16P_ACC_OUT(c) : M16P_IN_CARRY(a) : "memory", "scc", M16P_KLOOP_CLOBBERS);
+    M16P_KLOOP(M16P_BWD_DATA_ASM, "=&v", M16P_IN_CARRY(a));
 }
+#undef M16P_KLOOP
 
 // ------------------------------------------------------------------------------------------------
 // forward
@@ -867,7 +865,7 @@ __device__ __forceinline__ void mlp16s_fwd_hand_body(Mlp16Dev p, float* __restri
                 am[0][nt][4 * g + 0] = bv.x; am[0][nt][4 * g + 1] = bv.y; am[0][nt][4 * g + 2] = bv.z; am[0][nt][4 * g + 3] = bv.w;
             }
         {   // (no "products off" switch here: a second definition of the accumulators costs ~130 moves per layer in THIS path)
-            const Kloop16sAddr ka = kloop16s_addr(smem, wave, lane);
+            const Kloop16Addr ka = kloop16_addr<SP_W, 16>(smem, wave, lane);
             _Float16* st = TRAIN ? saved_hT + (size_t)(l > 0 ? l - 1 : 0) * layer_elems + (size_t)blockIdx.x * NS * M16_W * ROWS + wave * (NS * M16_W * T16_BLK) : nullptr;
             kloop16s_fwd<TRAIN>(ka, (const _Float16*)p.w[l] + wave * 1024, (const _Float16*)p.wlo[l] + wave * 1024, st, l == 0, am, ax);
         }
@@ -950,7 +948,7 @@ __device__ __forceinline__ void mlp16p_fwd_hand_body(Mlp16Dev p, float* __restri
                 c[0][nt][4 * g + 0] = bv.x; c[0][nt][4 * g + 1] = bv.y; c[0][nt][4 * g + 2] = bv.z; c[0][nt][4 * g + 3] = bv.w;
             }
         {
-            const Kloop16sAddr ka = kloop16p_addr(smem, wave, lane);
+            const Kloop16Addr ka = kloop16_addr<M16_W, 32>(smem, wave, lane);
             T* st = TRAIN ? saved_hT + (size_t)(l > 0 ? l - 1 : 0) * layer_elems + (size_t)blockIdx.x * M16_W * ROWS + wave * (2 * M16_W * T16_BLK) : nullptr;
             kloop16p_fwd<T, TRAIN>(ka, (const T*)p.w[l] + wave * 1024, st, l == 0, c);
         }
@@ -1234,7 +1232,7 @@ __device__ __forceinline__ void mlp16s_bwd_data_hand_body(Mlp16Dev p, const uint
         }
         f32x16 am[2][2], ax[2][2];
         {
-            const Kloop16sAddr ka = kloop16s_addr(smem, wave, lane);
+            const Kloop16Addr ka = kloop16_addr<SP_W, 16>(smem, wave, lane);
             _Float16* st = dzT + (size_t)(l < 4 ? l : 0) * layer_elems + (size_t)blockIdx.x * NS * M16_W * ROWS + wave * (NS * M16_W * T16_BLK);
             kloop16s_bwd(ka, (const _Float16*)p.w[l] + wave * 1024, (const _Float16*)p.wlo[l] + wave * 1024, st, l == 4, am, ax);
         }
@@ -1322,7 +1320,7 @@ __device__ __forceinline__ void mlp16p_bwd_data_hand_body(Mlp16Dev p, const uint
         }
         f32x16 c[4][2];
         {
-            const Kloop16sAddr ka = kloop16p_addr(smem, wave, lane);
+            const Kloop16Addr ka = kloop16_addr<M16_W, 32>(smem, wave, lane);
             T* st = dzT + (size_t)(l < 4 ? l : 0) * layer_elems + (size_t)blockIdx.x * M16_W * ROWS + wave * (2 * M16_W * T16_BLK);
             kloop16p_bwd<T>(ka, (const T*)p.w[l] + wave * 1024, st, l == 4, c);
         }
