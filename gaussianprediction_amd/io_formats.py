@@ -10,6 +10,8 @@ in the other:
 * `chkpnt<iteration>.pth` = `torch.save((gaussians.state_dict(), optimizer.state_dict(), iteration))`
   [REF train.py:199-201], restored with `load_state_dict(strict=False)` after sizing the model from `_xyz` /
   `super_gaussians` [REF train.py:48-57].  Parameter names are identical here, so the tuple is interchangeable.
+* the point cloud a scene starts from, as Open3D's `write_point_cloud` lays a binary PLY out (`save_point_cloud_ply`: double
+  `x y z`, double normals, uchar colours), which the reference's `fetchPly` reads [REF scene/dataset_readers.py:112-118].
 """
 from __future__ import annotations
 
@@ -92,6 +94,40 @@ def read_ply_vertices(path):
                 out[name] = rows[:, k]
             return out
         raise ValueError(f"{path}: unsupported PLY format {fmt}")
+
+
+def color_to_uint8(colors):
+    """round(clamp(c, 0, 1) * 255) as uint8: Open3D's ColorToUint8, restated from memory of its source (Open3D is not installed where
+    this was written, so the rounding of an exact half is unpinned; np.round sends it to the even byte)."""
+    return np.round(np.clip(np.asarray(colors, dtype=np.float64), 0.0, 1.0) * 255.0).astype(np.uint8)
+
+
+def save_point_cloud_ply(path, points, colors=None, normals=None):
+    """A point cloud as Open3D's write_point_cloud lays a binary PLY out: little-endian, one `vertex` element, double x y z, double
+    nx ny nz where there are normals, uchar red green blue = color_to_uint8(colors) where there are colours -- the field names the
+    reference's fetchPly reads [REF scene/dataset_readers.py:112-118].  points / colors / normals: [N, 3] arrays."""
+    cols = [("x", "<f8"), ("y", "<f8"), ("z", "<f8")]
+    points = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    parts = [(("x", "y", "z"), points)]
+    if normals is not None:
+        cols += [("nx", "<f8"), ("ny", "<f8"), ("nz", "<f8")]
+        parts.append((("nx", "ny", "nz"), np.asarray(normals, dtype=np.float64).reshape(-1, 3)))
+    if colors is not None:
+        cols += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+        parts.append((("red", "green", "blue"), color_to_uint8(colors).reshape(-1, 3)))
+    table = np.empty(points.shape[0], dtype=np.dtype(cols))
+    for names, a in parts:
+        if a.shape != points.shape:
+            raise ValueError(f"save_point_cloud_ply: {names} are {a.shape}, the points {points.shape}")
+        for k, name in enumerate(names):
+            table[name] = a[:, k]
+    kinds = {"<f8": "double", "u1": "uchar"}
+    header = "ply\nformat binary_little_endian 1.0\n" + f"element vertex {table.shape[0]}\n" + \
+        "".join(f"property {kinds[t]} {n}\n" for n, t in cols) + "end_header\n"
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "wb") as f:
+        f.write(header.encode("ascii"))
+        f.write(table.tobytes())
 
 
 def load_ply(path, sh_degree=3, device="cpu"):
