@@ -230,15 +230,12 @@ ABIS = []                  # every Abi, in import order; the main one (include/g
 class Abi:
     """One header of include/ and its binding: the header's file name, the name of its *_abi_version function, the version this
     binding is written against, and {name: (restype, argtypes)} as the header declares them (tests/abi_check.py compares the two).
-    Constructing one registers it in ABIS; lib() applies the table to the one CDLL handle and checks the version, once.
-    register=False keeps a table out of ABIS: the headers of include/ext/ (`header` is then "ext/<name>.h"), which the test of their
-    own module checks."""
+    Constructing one registers it in ABIS; lib() applies the table to the one CDLL handle and checks the version, once."""
 
-    def __init__(self, header, version_fn, version, prototypes, register=True):
+    def __init__(self, header, version_fn, version, prototypes):
         self.header, self.version_fn, self.version, self.prototypes = header, version_fn, version, prototypes
         self._handle = None
-        if register:
-            ABIS.append(self)
+        ABIS.append(self)
 
     def bind(self, l):
         rebuild = "rebuild the library (__graft_entry__.build(force=True))"

@@ -1,4 +1,4 @@
-// resize_core.h -- Pillow's 8-bit resampler (include/ext/gp_resize.h) in this repository's own words: the coefficient builder, which
+// resize_core.h -- Pillow's 8-bit resampler (include/gp_resize.h) in this repository's own words: the coefficient builder, which
 // runs on the host in double, and the integer pass of one output sample, which runs on the device and, for the host tests
 // (tests/resize_emulate.cpp, under the sanitizers), on a CPU.  Nothing here is a tolerance: the tables and the bytes are Pillow's.
 //
@@ -13,7 +13,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 
-#include "../../include/ext/gp_resize.h"
+#include "../../include/gp_resize.h"
 
 #if defined(__HIPCC__)
 #define RS_FN __host__ __device__ inline

@@ -1,4 +1,4 @@
-// resize_kernels.hip -- Pillow-exact 8-bit resizing on the device (include/ext/gp_resize.h).  The arithmetic is csrc/resize_core.h.
+// resize_kernels.hip -- Pillow-exact 8-bit resizing on the device (include/gp_resize.h).  The arithmetic is csrc/resize_core.h.
 //   rs_fused_kernel        one workgroup of 256 lanes per tile of 64 x 32 output pixels of one plane (of all four planes with
 //                          alpha_mode, alpha first): the tile's coefficients go to LDS, the horizontal pass of the source rows the tile
 //                          needs goes to LDS as bytes, the vertical pass reads them there; the intermediate never reaches memory

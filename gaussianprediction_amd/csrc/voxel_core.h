@@ -1,4 +1,4 @@
-// voxel_core.h -- the arithmetic of the voxel-grid downsample (include/ext/gp_voxel.h), shared by the kernels of voxel_kernels.hip and
+// voxel_core.h -- the arithmetic of the voxel-grid downsample (include/gp_voxel.h), shared by the kernels of voxel_kernels.hip and
 // by the host pass gp_voxel_downsample_host, which the tests without a device run (and tests/voxel_emulate.cpp, under the sanitizers).
 //
 //   vx_finite / vx_index               the non-finite test on the bits, and index = (int32)floor((p - min_bound) / voxel_size)
@@ -15,7 +15,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "../../include/ext/gp_voxel.h"
+#include "../../include/gp_voxel.h"
 
 #if defined(__HIPCC__)
 #define VX_FN __host__ __device__ inline

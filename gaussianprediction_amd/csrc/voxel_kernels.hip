@@ -1,4 +1,4 @@
-// voxel_kernels.hip -- voxel-grid downsampling of a point cloud on the device (include/ext/gp_voxel.h).  The arithmetic is
+// voxel_kernels.hip -- voxel-grid downsampling of a point cloud on the device (include/gp_voxel.h).  The arithmetic is
 // csrc/voxel_core.h, which also runs on a CPU (gp_voxel_downsample_host, tests/voxel_emulate.cpp).
 //   vx_bounds_partial_kernel   up to 1024 workgroups stride over the points: per-lane min / max of each axis and the non-finite flag,
 //                              reduced through LDS, one row of seven doubles per workgroup

@@ -1,4 +1,4 @@
-"""Image resizing on the device, byte for byte what Pillow's Image.resize returns (include/ext/gp_resize.h, csrc/resize_kernels.hip):
+"""Image resizing on the device, byte for byte what Pillow's Image.resize returns (include/gp_resize.h, csrc/resize_kernels.hip):
 the step between decoding an image file and scoring or training on it at a reduced resolution.
 
   [REF metrics.py readImages]              Image.open(f).resize((int(w * ratio), int(h * ratio))), then to_tensor and [:, :3]
@@ -8,9 +8,7 @@ Pillow's 8-bit resampler is integer arithmetic once its coefficient tables exist
 and an 8-bit rounding between them.  The tables are built on the host in double (gp_resize_coeffs) and cached on the device per
 (device, in, out, filter); the passes run in one fused launch with the intermediate in LDS, or in two launches through a scratch
 buffer where a tile's window does not fit (gp_resize_path tells which).  RGBA goes through premultiplied alpha as Image.resize sends
-it.  HIP only: CPU tensors raise.
-
-The header sits in include/ext/ and the table below is built with register=False: _lib.ABIS stays the ten headers of include/."""
+it.  HIP only: CPU tensors raise."""
 from __future__ import annotations
 
 import ctypes as C
@@ -20,7 +18,7 @@ import torch
 
 from . import _lib
 
-GP_RESIZE_ABI_VERSION = 1           # include/ext/gp_resize.h
+GP_RESIZE_ABI_VERSION = 1           # include/gp_resize.h
 LANCZOS, BILINEAR, BICUBIC, BOX, HAMMING = 1, 2, 3, 4, 5      # Pillow's Image.Resampling values
 FILTERS = {"lanczos": LANCZOS, "bilinear": BILINEAR, "bicubic": BICUBIC, "box": BOX, "hamming": HAMMING}
 DST_U8, DST_F32 = 0, 1
@@ -32,7 +30,7 @@ TABLE_CACHE = 64                    # axes kept on the device
 
 def _prototypes():
     i32, i64, P = C.c_int32, C.c_int64, _lib.Ptr
-    return {   # name: (restype, argtypes), as include/ext/gp_resize.h declares them (tests/test_resize_host.py compares the two)
+    return {   # name: (restype, argtypes), as include/gp_resize.h declares them (tests/test_resize_host.py compares the two)
         "gp_resize_abi_version": (i32, []),
         "gp_resize_ksize": (i32, [i32, i32, i32]),
         "gp_resize_coeffs": (i32, [i32, i32, i32, P, P]),
@@ -43,7 +41,7 @@ def _prototypes():
 
 
 PROTOTYPES = _prototypes()
-ABI = _lib.Abi("ext/gp_resize.h", "gp_resize_abi_version", GP_RESIZE_ABI_VERSION, PROTOTYPES, register=False)
+ABI = _lib.Abi("gp_resize.h", "gp_resize_abi_version", GP_RESIZE_ABI_VERSION, PROTOTYPES)
 lib = ABI.lib            # the handle of _lib.lib() with this table applied (once)
 
 _tables: dict = {}

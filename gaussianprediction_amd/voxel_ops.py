@@ -1,4 +1,4 @@
-"""Voxel-grid downsampling of a point cloud on the device (include/ext/gp_voxel.h, csrc/voxel_kernels.hip): the step that makes the
+"""Voxel-grid downsampling of a point cloud on the device (include/gp_voxel.h, csrc/voxel_kernels.hip): the step that makes the
 cloud a HyperNeRF scene starts from.
 
   [REF utils/prepare/downsample_points.py]   voxel_size = 0.02; while len(pcd.points) > 40000: pcd = pcd.voxel_down_sample(voxel_size);
@@ -16,9 +16,7 @@ the previous pass wrote, its sums can differ from Open3D's in the last bit.
 One pass: two launches for the bounds, then a read of 64 bytes (the refusals -- a coordinate that is not finite, "voxel_size is too
 small" -- are raised on it before any coordinate is converted to an integer, and the sort key takes only the bits the largest index
 needs); the index, the sort, the segment heads and the means are launched without another look at the device; then a read of M.
-HIP only: CPU tensors raise.
-
-The header sits in include/ext/ and the table below is built with register=False: _lib.ABIS stays the ten headers of include/."""
+HIP only: CPU tensors raise."""
 from __future__ import annotations
 
 import ctypes as C
@@ -29,14 +27,14 @@ import torch
 
 from . import _lib, io_formats
 
-GP_VOXEL_ABI_VERSION = 1            # include/ext/gp_voxel.h
+GP_VOXEL_ABI_VERSION = 1            # include/gp_voxel.h
 RECORD_DOUBLES = 8                  # min x y z, max x y z, the non-finite flag, 0
 MAX_N = 2 ** 31 - 1                 # n below this
 
 
 def _prototypes():
     i32, i64, f64, P = C.c_int32, C.c_int64, C.c_double, _lib.Ptr
-    return {   # name: (restype, argtypes), as include/ext/gp_voxel.h declares them (tests/test_voxel_host.py compares the two)
+    return {   # name: (restype, argtypes), as include/gp_voxel.h declares them (tests/test_voxel_host.py compares the two)
         "gp_voxel_abi_version": (i32, []),
         "gp_voxel_scratch_bytes": (i64, [i64]),
         "gp_voxel_bounds": (i32, [i64, P, P, P, P]),
@@ -46,7 +44,7 @@ def _prototypes():
 
 
 PROTOTYPES = _prototypes()
-ABI = _lib.Abi("ext/gp_voxel.h", "gp_voxel_abi_version", GP_VOXEL_ABI_VERSION, PROTOTYPES, register=False)
+ABI = _lib.Abi("gp_voxel.h", "gp_voxel_abi_version", GP_VOXEL_ABI_VERSION, PROTOTYPES)
 lib = ABI.lib            # the handle of _lib.lib() with this table applied (once)
 
 

@@ -1,10 +1,6 @@
 /* gp_resize.h -- Pillow-exact image resizing on the device, for the metrics and the loaders that score or train at a reduced
  * resolution: the C entry points of csrc/resize_kernels.hip, a part of libgp_hip.so with an ABI number of its own.
  *
- * This header lives in include/ext/, not in include/: the headers directly inside include/ are the ten whose bindings register in
- * _lib.ABIS, a set the ABI tests pin by listing that directory.  The binding of this one (gaussianprediction_amd/resize_ops.py) is
- * the same Abi class with register=False, checked by tests/test_resize_host.py.
- *
  * Conventions are those of gp_hip.h: plain device pointers and sizes, a return code != 0 (or -1 from a query) plus gp_last_error(),
  * no synchronisation and no host read inside any entry, a gp_stream_t last.  Nothing is atomic and nothing depends on an order: two
  * calls on equal inputs give equal bytes, and image b of a batch gives the bytes of the B = 1 call on that image.
@@ -28,7 +24,7 @@
 #ifndef GP_RESIZE_H
 #define GP_RESIZE_H
 
-#include "../gp_hip.h"
+#include "gp_hip.h"
 
 #ifdef __cplusplus
 extern "C" {

@@ -1,10 +1,6 @@
 /* gp_voxel.h -- voxel-grid downsampling of a point cloud on the device, in the semantics of Open3D's PointCloud::VoxelDownSample:
  * the C entry points of csrc/voxel_kernels.hip, a part of libgp_hip.so with an ABI number of its own.
  *
- * This header lives in include/ext/, not in include/: the headers directly inside include/ are the ten whose bindings register in
- * _lib.ABIS.  The binding of this one (gaussianprediction_amd/voxel_ops.py) is the same Abi class with register=False, checked by
- * tests/test_voxel_host.py.
- *
  * What it replaces: pcd.voxel_down_sample(voxel_size) in the loop of [REF utils/prepare/downsample_points.py], which makes the
  * points3D_downsample.ply that [REF scene/dataset_readers.py:294] opens.  Open3D is not installed where this was written: the
  * semantics below are restated from its published source and parity with its binary is unpinned.
@@ -31,7 +27,7 @@
 #ifndef GP_VOXEL_H
 #define GP_VOXEL_H
 
-#include "../gp_hip.h"
+#include "gp_hip.h"
 
 #ifdef __cplusplus
 extern "C" {

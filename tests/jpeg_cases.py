@@ -1,14 +1,11 @@
 """Shared by tests/test_jpeg_host.py (the encoder's workgroup programs emulated on the CPU) and tests/test_gpu_jpeg.py (the kernels): the
 images -- the smallest shapes at which each mechanism of include/gp_jpeg.h can go wrong -- and their quantisation tables."""
-import os
-import shutil
 import subprocess
 
 import numpy as np
 
+import emulate_build
 import png_cases as P
-
-HERE = os.path.dirname(os.path.abspath(__file__))
 
 ONES = [1] * 64
 
@@ -90,11 +87,7 @@ def cases():
 def build_emulator(d):
     """tests/jpeg_emulate.cpp built with the host compiler into directory `d`; returns run(img [3, H, W], "420" / "444", (luminance,
     chrominance) tables, key=None) -> the file's bytes (kept per key)."""
-    cxx = next((c for c in (os.environ.get("CXX"), shutil.which("c++"), shutil.which("g++"), shutil.which("clang++"),
-                            "/opt/rocm/lib/llvm/bin/clang++", "/opt/rocm/llvm/bin/clang++") if c and (os.path.sep not in c or os.path.exists(c))), None)
-    assert cxx, "no host C++ compiler"
-    exe = str(d / "jpeg_emulate")
-    subprocess.check_call([cxx, "-O2", "-std=c++17", "-ffp-contract=off", "-o", exe, os.path.join(HERE, "jpeg_emulate.cpp")], timeout=300)
+    exe = emulate_build.build("jpeg_emulate", d)
     done = {}
 
     def run(img, sub, qtables, key=None):

@@ -4,10 +4,12 @@ a writer the caller passes (tests/jpeg_emulate.cpp on the CPU, jpeg_ops on the d
 files derived from good ones; and the files the host refuses."""
 import io
 import struct
+import subprocess
 from types import SimpleNamespace
 
 import numpy as np
 
+import emulate_build
 import jpeg_cases as J
 import jpeg_ref as R
 
@@ -238,3 +240,62 @@ def refused(own):
     out.append(("no-eoi", own_file[:-2], "no EOI"))
     out.append(("not-a-jpeg", b"\x89PNG" + own_file[4:], "no SOI"))
     return out
+
+
+def run_job(exe, d, JD, items, group, dtype, guard, mangle=None, most=None):
+    """One process of tests/jpeg_decode_emulate.cpp or tests/jpeg_sync_emulate.cpp (they read the same job file) over one shape group of
+    JD.groups(items) -> the bytes it wrote."""
+    (H, W, sub), idx = group
+    seg, image_seg, copies, nbytes, top = JD.tables(items, idx)
+    seg = seg if mangle is None else mangle([tuple(r) for r in seg.tolist()])
+    payload = bytearray(nbytes)
+    for at, piece in copies:
+        payload[at:at + len(piece)] = piece
+    job, out = str(d / "job.bin"), str(d / "out.bin")
+    with open(job, "wb") as fp:
+        fp.write(struct.pack("<8iq", len(idx), H, W, sub, 0 if dtype == np.uint8 else 1, len(seg), top if most is None else most, guard, nbytes))
+        fp.write(np.array(seg, dtype=np.int64).tobytes() + np.array(image_seg, dtype=np.int32).tobytes() + b"".join(items[i].tables for i in idx)
+                 + bytes(payload))
+    subprocess.check_call([exe, job, out], timeout=300)          # (a loop that does not end is a failure here, not a hang)
+    return open(out, "rb").read()
+
+
+def build_emulator(d, sanitize):
+    """tests/jpeg_decode_emulate.cpp built into directory `d`; returns run(items, dtype, guard, mangle, most) -> (images [3, H, W] numpy,
+    status), one process per shape group."""
+    from gaussianprediction_amd import jpeg_decode as JD
+    exe = emulate_build.build("jpeg_decode_emulate", d, sanitize)
+
+    def run(items, dtype=np.uint8, guard=8, mangle=None, most=None):
+        images, status = [None] * len(items), [0] * len(items)
+        for group in JD.groups(items):
+            (H, W, _), idx = group
+            raw = run_job(exe, d, JD, items, group, dtype, guard, mangle, most)
+            B, n = len(idx), 3 * H * W
+            words = np.frombuffer(raw[:4 * B], dtype=np.uint32)
+            slots = np.frombuffer(raw[4 * B:], dtype=dtype).reshape(B, n + guard)
+            assert (slots[:, n:].view(np.uint8) == 0xA5).all()          # the guard behind every slot
+            for b, i in enumerate(idx):
+                status[i] = int(words[b])
+                images[i] = slots[b, :n].reshape(3, H, W)
+        return images, status
+
+    return run
+
+
+def eval_directory(root, H, W, dev):
+    """What metrics.evaluate_dirs reads, for the device tests: two methods of four .png renders and .jpg ground truths each, one with this
+    project's JPEG files (written on `dev`) and one with Pillow's."""
+    import torch
+    from PIL import Image
+    from gaussianprediction_amd import jpeg_ops, png_ops
+    for method, own in (("ours", True), ("theirs", False)):
+        for sub in ("renders", "gt"):
+            (root / method / sub).mkdir(parents=True)
+        for i in range(4):
+            render, gt = J.textured(H, W, 10 * i + own), J.textured(H, W, 10 * i + 5)
+            (root / method / "renders" / f"{i:05d}.png").write_bytes(png_ops.encode_to_bytes(torch.from_numpy(render).to(dev))[0])
+            if own:
+                (root / method / "gt" / f"{i:05d}.jpg").write_bytes(jpeg_ops.encode_to_bytes(torch.from_numpy(gt).to(dev), subsampling="420" if i % 2 else "444")[0])
+            else:
+                Image.fromarray(gt.transpose(1, 2, 0)).save(root / method / "gt" / f"{i:05d}.jpg", quality=92, subsampling=2 if i % 2 else 0)

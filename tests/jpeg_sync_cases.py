@@ -6,6 +6,7 @@ from types import SimpleNamespace
 
 import numpy as np
 
+import emulate_build
 import jpeg_cases as J
 import jpeg_decode_cases as D
 import jpeg_sync_ref as SR
@@ -152,3 +153,25 @@ def malformed():
     bits[0], bits[2] = 2, bits[2] - 2
     case("oversubscribed-dht", base[:at + 5] + bytes(bits) + base[at + 21:], D.HUFFMAN_TABLE)
     return out
+
+
+def build_emulator(d, sanitize):
+    """tests/jpeg_sync_emulate.cpp built into directory `d`; returns run(items, dtype, guard) -> (images [3, H, W] numpy, status, info)."""
+    from gaussianprediction_amd import jpeg_decode as JD
+    exe = emulate_build.build("jpeg_sync_emulate", d, sanitize)
+
+    def run(items, dtype=np.uint8, guard=8):
+        images, status, info = [None] * len(items), [0] * len(items), [None] * len(items)
+        for group in JD.groups(items):
+            (H, W, _), idx = group
+            raw = D.run_job(exe, d, JD, items, group, dtype, guard)
+            B, n = len(idx), 3 * H * W
+            words = np.frombuffer(raw[:4 * B], dtype=np.uint32)
+            infos = np.frombuffer(raw[4 * B:20 * B], dtype=np.uint32).reshape(B, 4)
+            slots = np.frombuffer(raw[20 * B:], dtype=dtype).reshape(B, n + guard)
+            assert (slots[:, n:].view(np.uint8) == 0xA5).all()          # the guard behind every slot
+            for b, i in enumerate(idx):
+                status[i], info[i], images[i] = int(words[b]), tuple(int(v) for v in infos[b]), slots[b, :n].reshape(3, H, W)
+        return images, status, info
+
+    return run

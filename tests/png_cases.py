@@ -3,9 +3,12 @@ images, the 8-bit quantisation in numpy, the chunk walk with zlib's and Pillow's
 reference (zlib's own run-length strategy over the same filtered bytes, cut at the same bands)."""
 import io
 import struct
+import subprocess
 import zlib
 
 import numpy as np
+
+import emulate_build
 
 SIGNATURE = b"\x89PNG\r\n\x1a\n"
 
@@ -239,3 +242,18 @@ def rle_reference_bytes(stream, band):
         c = zlib.compressobj(1, zlib.DEFLATED, -15, 9, zlib.Z_RLE)
         total += len(c.compress(stream[k:k + band]) + c.flush(zlib.Z_SYNC_FLUSH))
     return total
+
+
+def build_emulator(d):
+    """tests/png_emulate.cpp built into directory `d`; returns run(img [3, H, W], filter_none) -> the file's bytes."""
+    exe = emulate_build.build("png_emulate", d)
+
+    def run(img, filter_none):
+        src, out = str(d / "in.raw"), str(d / "out.png")
+        np.ascontiguousarray(img).tofile(src)
+        _, H, W = img.shape
+        subprocess.check_call([exe, str(H), str(W), "1" if img.dtype == np.uint8 else "0", "1" if filter_none else "0", src, out],
+                              timeout=60)          # (a phase that does not end is a failure here, not a hang)
+        return open(out, "rb").read()
+
+    return run

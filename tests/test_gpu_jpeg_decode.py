@@ -6,10 +6,6 @@ malformed file is refused with its status between two good images, jpeg_ops.enco
 the same bytes, decode_avi equals Pillow frame by frame, and evaluate_dirs(device_decode=True) equals the default path key for key
 and float for float."""
 import json
-import os
-import shutil
-import struct
-import subprocess
 
 import numpy as np
 import pytest
@@ -22,7 +18,6 @@ pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
 GUARD = 16
-HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 @pytest.fixture(scope="module")
@@ -52,37 +47,10 @@ def well(own):
 
 
 @pytest.fixture(scope="module")
-def emulate(JD, tmp_path_factory):
+def emulate(tmp_path_factory):
     """emulate(items) -> (images [3, H, W] numpy, status): csrc/jpeg_decode_core.h on the CPU (tests/jpeg_decode_emulate.cpp, built plain)."""
-    d = tmp_path_factory.mktemp("jpeg_decode_emulate")
-    cxx = next((c for c in (os.environ.get("CXX"), shutil.which("c++"), shutil.which("g++"), shutil.which("clang++"),
-                            "/opt/rocm/lib/llvm/bin/clang++", "/opt/rocm/llvm/bin/clang++") if c and (os.path.sep not in c or os.path.exists(c))), None)
-    assert cxx, "no host C++ compiler"
-    exe = str(d / "jpeg_decode_emulate")
-    subprocess.check_call([cxx, "-O2", "-std=c++17", "-ffp-contract=off", "-o", exe, os.path.join(HERE, "jpeg_decode_emulate.cpp")], timeout=300)
-
-    def run(items):
-        images, status = [None] * len(items), [0] * len(items)
-        for (H, W, sub), idx in JD.groups(items):
-            seg, image_seg, copies, nbytes, most = JD.tables(items, idx)
-            payload = bytearray(nbytes)
-            for at, piece in copies:
-                payload[at:at + len(piece)] = piece
-            job, out = str(d / "job.bin"), str(d / "out.bin")
-            with open(job, "wb") as fp:
-                fp.write(struct.pack("<8iq", len(idx), H, W, sub, 0, len(seg), most, 0, nbytes))
-                fp.write(np.array(seg, dtype=np.int64).tobytes() + np.array(image_seg, dtype=np.int32).tobytes() + b"".join(items[i].tables for i in idx)
-                         + bytes(payload))
-            subprocess.check_call([exe, job, out], timeout=120)
-            raw = open(out, "rb").read()
-            B = len(idx)
-            words = np.frombuffer(raw[:4 * B], dtype=np.uint32)
-            slots = np.frombuffer(raw[4 * B:], dtype=np.uint8).reshape(B, 3 * H * W)
-            for b, i in enumerate(idx):
-                status[i], images[i] = int(words[b]), slots[b].reshape(3, H, W)
-        return images, status
-
-    return run
+    run = D.build_emulator(tmp_path_factory.mktemp("jpeg_decode_emulate"), sanitize=False)
+    return lambda items: run(items, guard=0)
 
 
 def _once(JD, files, **kw):
@@ -181,33 +149,18 @@ def test_decode_avi_equals_pillow_frame_by_frame(JD, tmp_path):
         JD.decode_avi(path, device=DEV, frames=[5])
 
 
-def _directory(root, H, W):
-    from PIL import Image
-    from gaussianprediction_amd import jpeg_ops, png_ops
-    for method, own in (("ours", True), ("theirs", False)):
-        for sub in ("renders", "gt"):
-            (root / method / sub).mkdir(parents=True)
-        for i in range(4):
-            render, gt = J.textured(H, W, 10 * i + own), J.textured(H, W, 10 * i + 5)
-            (root / method / "renders" / f"{i:05d}.png").write_bytes(png_ops.encode_to_bytes(torch.from_numpy(render).to(DEV))[0])
-            if own:
-                (root / method / "gt" / f"{i:05d}.jpg").write_bytes(jpeg_ops.encode_to_bytes(torch.from_numpy(gt).to(DEV), subsampling="420" if i % 2 else "444")[0])
-            else:
-                Image.fromarray(gt.transpose(1, 2, 0)).save(root / method / "gt" / f"{i:05d}.jpg", quality=92, subsampling=2 if i % 2 else 0)
-
-
 def test_evaluate_dirs_with_device_decode_gives_the_default_paths_numbers(JD, tmp_path):
     """Four pairs of .png renders and .jpg ground truth, two methods: one with this project's JPEG files, one with Pillow's (no
     restart markers: the serial path).  At 48 x 64 both paths refuse alike (MS-SSIM needs min(H, W) > 160, as on the parent commit),
     so the dictionaries are compared at the smallest size the default path scores, 163 x 178."""
     from gaussianprediction_amd import _lib, metrics as M
     small = tmp_path / "small"
-    _directory(small, 48, 64)
+    D.eval_directory(small, 48, 64, DEV)
     for kw in (dict(), dict(device_decode=True)):
         with pytest.raises(_lib.GpHipError, match="MS-SSIM needs"):
             M.evaluate_dirs(str(small), device=DEV, **kw)
     root = tmp_path / "run"
-    _directory(root, 163, 178)
+    D.eval_directory(root, 163, 178, DEV)
     want = M.evaluate_dirs(str(root), device=DEV)
     files = [json.load(open(root / n)) for n in ("results.json", "per_view.json")]
     for kw in (dict(), dict(png_group=3), dict(png_group=1)):

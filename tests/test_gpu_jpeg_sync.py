@@ -35,8 +35,7 @@ def JS():
 @pytest.fixture(scope="module")
 def emulate(tmp_path_factory):
     """csrc/jpeg_sync_core.h on the CPU (tests/jpeg_sync_emulate.cpp, built plain): run(items) -> (images, status, info)."""
-    from test_jpeg_sync_host import build_emulator
-    return build_emulator(tmp_path_factory.mktemp("jpeg_sync_emulate"), sanitize=False)
+    return SC.build_emulator(tmp_path_factory.mktemp("jpeg_sync_emulate"), sanitize=False)
 
 
 @pytest.fixture(scope="module")
@@ -153,9 +152,8 @@ def test_decode_files_and_decode_avi_with_sync_equal_the_one_lane_results(JD, tm
 
 
 def test_evaluate_dirs_with_decode_sync_gives_the_same_numbers(tmp_path):
-    from test_gpu_jpeg_decode import _directory
     from gaussianprediction_amd import metrics as M
     root = tmp_path / "run"
-    _directory(root, 163, 178)
+    D.eval_directory(root, 163, 178, DEV)
     want = M.evaluate_dirs(str(root), device=DEV, device_decode=True, write=False)
     assert M.evaluate_dirs(str(root), device=DEV, device_decode=True, decode_sync=True, write=False) == want

@@ -1,4 +1,4 @@
-"""Image resizing on the device (include/ext/gp_resize.h, resize_ops): byte for byte what Pillow's Image.resize returns -- the smallest
+"""Image resizing on the device (include/gp_resize.h, resize_ops): byte for byte what Pillow's Image.resize returns -- the smallest
 cases, the fused path's tile edges, an upscale, the reference's own rounding, the two-launch path, all five filters, L / RGB / RGBA,
 batches with a free batch stride, both destination kinds, the workload's shape; the decoders' resize= against Pillow-open followed by
 Pillow-resize; and evaluate_dirs(resize=True) equal, number for number, to scoring files that Pillow resized on the host.  Sizes are

@@ -1,4 +1,4 @@
-"""Voxel-grid downsampling on the device (include/ext/gp_voxel.h, voxel_ops) against the numpy restatement tests/voxel_ref.py, bit for
+"""Voxel-grid downsampling on the device (include/gp_voxel.h, voxel_ops) against the numpy restatement tests/voxel_ref.py, bit for
 bit: every size at which the sort or the scan takes another path, with and without colours and normals; points exactly on voxel
 boundaries, negative coordinates, duplicates; one voxel holding every point, every point in its own voxel, keys of one, two and three
 sorts; the reference's loop; determinism, the voxel indices, the PLY tool against the host path's file; the refusals.  There are no

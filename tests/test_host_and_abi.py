@@ -258,9 +258,9 @@ _POINTEES = {"float", "double", "void", "int", "int8_t", "int16_t", "int32_t", "
 
 
 def _abis():
-    """Every registered binding: the nine further modules join _lib.ABIS when they are imported."""
+    """Every binding: the eleven further modules join _lib.ABIS when they are imported."""
     from gaussianprediction_amd import (densify_ops, gcn_ops, jpeg_decode, jpeg_ops, jpeg_sync, kmeans_ops, lpips,  # noqa: F401
-                                        png_decode, png_ops)
+                                        png_decode, png_ops, resize_ops, voxel_ops)
     return _lib.ABIS
 
 
@@ -280,9 +280,9 @@ def test_prototype_table_is_applied_to_the_library():
 def test_every_header_has_one_binding_and_no_name_two():
     abis = _abis()
     headers = sorted(a.header for a in abis)
-    assert headers == sorted(f for f in os.listdir(os.path.join(ROOT, "include")) if f.endswith(".h")), headers
+    assert headers == sorted(os.listdir(os.path.join(ROOT, "include"))) and len(headers) == 12, headers       # (twelve .h files, no directory)
     names = [n for a in abis for n in a.prototypes]
-    assert len(names) == len(set(names)) == 106, sorted(n for n in set(names) if names.count(n) > 1)
+    assert len(names) == len(set(names)) == 117, sorted(n for n in set(names) if names.count(n) > 1)
 
 
 def test_argument_width_survives_without_a_wrapper():
@@ -321,7 +321,7 @@ def test_wrong_argument_kinds_are_refused_before_the_library_runs():
 
 def test_every_call_site_passes_as_many_arguments_as_the_prototype_has():
     """ctypes accepts surplus positional arguments in silence and most call sites only run on a GPU: count them in the source, for
-    every registered table.  A call site is `x.gp_name(...)`, `q(...)` where the file binds `q = x.gp_name`, and
+    every table, and find every entry point called somewhere.  A call site is `x.gp_name(...)`, `q(...)` where the file binds `q = x.gp_name`, and
     `_lib.scratch(x.gp_name, ...)`, which calls its first argument with the further positional ones."""
     import ast
     import glob
@@ -329,7 +329,8 @@ def test_every_call_site_passes_as_many_arguments_as_the_prototype_has():
     files = [os.path.join(ROOT, "bench.py"), os.path.join(ROOT, "__graft_entry__.py")]
     for d in ("gaussianprediction_amd", "tools", "tests"):
         files += glob.glob(os.path.join(ROOT, d, "**", "*.py"), recursive=True)
-    examined = {abi.header: 0 for abi in _abis()}
+    examined, seen = {abi.header: 0 for abi in _abis()}, set()
+    uncalled = {abi.version_fn for abi in _abis()} | {"gp_adam_step"}       # Abi.bind calls version_fn through getattr; nothing in Python calls gp_adam_step
     for path in sorted(files):
         nodes, alias = list(ast.walk(ast.parse(open(path).read(), path))), {}
         for node in nodes:
@@ -350,8 +351,12 @@ def test_every_call_site_passes_as_many_arguments_as_the_prototype_has():
                 if any(isinstance(a, ast.Starred) for a in args):
                     continue
                 examined[abi.header] += 1
+                seen.add(name)
                 assert len(args) == want, (os.path.relpath(path, ROOT), node.lineno, name)
     assert sum(examined.values()) >= 300 and all(examined.values()), examined
+    print(f"{sum(examined.values())} call sites of {len(seen)} entry points")
+    assert seen >= set(table) - uncalled, sorted(set(table) - uncalled - seen)
+    assert "gp_adam_step" not in seen                                      # (the exception goes when a call site comes)
 
 
 def test_allocator_block_releases_on_every_path_and_prefers_the_callback_error():

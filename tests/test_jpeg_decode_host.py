@@ -1,11 +1,9 @@
 """No GPU: include/gp_jpeg_decode.h against the binding's table; the refusals that need no device; the JPEG decoder's workgroup programs
-(csrc/jpeg_decode_core.h) run lane by lane on the CPU (tests/jpeg_decode_emulate.cpp, under -fsanitize=address,undefined where the host
-compiler can link that) over every case of tests/jpeg_decode_cases.py, with Pillow's decoder and tests/jpeg_decode_ref.py -- the header's
+(csrc/jpeg_decode_core.h) run lane by lane on the CPU (tests/jpeg_decode_emulate.cpp, under the sanitizers where the host compiler
+can link them) over every case of tests/jpeg_decode_cases.py, with Pillow's decoder and tests/jpeg_decode_ref.py -- the header's
 arithmetic in numpy -- as the oracles for the pixels.  Every comparison is bit-exact."""
 import ctypes as C
-import os
 import re
-import shutil
 import struct
 import subprocess
 
@@ -19,8 +17,6 @@ import jpeg_decode_cases as D
 import jpeg_decode_ref as REF
 import jpeg_ref as R
 from gaussianprediction_amd import _lib, jpeg_decode as JD
-
-HERE = os.path.dirname(os.path.abspath(__file__))
 
 _SCALARS = {"int": C.c_int32, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint32_t": C.c_uint32, "gp_stream_t": _lib.Ptr}
 _POINTEES = {"void", "uint8_t", "uint32_t", "int64_t", "int32_t", "float"}
@@ -67,13 +63,6 @@ def test_c_entries_refuse_before_they_look_at_a_pointer():
 
 
 # ---- the files ----
-def _compiler():
-    cxx = next((c for c in (os.environ.get("CXX"), shutil.which("c++"), shutil.which("g++"), shutil.which("clang++"),
-                            "/opt/rocm/lib/llvm/bin/clang++", "/opt/rocm/llvm/bin/clang++") if c and (os.path.sep not in c or os.path.exists(c))), None)
-    assert cxx, "no host C++ compiler"
-    return cxx
-
-
 @pytest.fixture(scope="module")
 def own(tmp_path_factory):
     """own(img [3, H, W] uint8, "420" / "444", quality or (luminance, chrominance), key) -> the file the encoder's workgroup programs
@@ -96,41 +85,8 @@ def own(tmp_path_factory):
 
 @pytest.fixture(scope="module")
 def emulator(tmp_path_factory):
-    """run(items, dtype, guard, mangle) -> (images [3, H, W] numpy, status), one process per shape group."""
-    cxx, d = _compiler(), tmp_path_factory.mktemp("jpeg_decode_emulate")
-    exe, probe = str(d / "jpeg_decode_emulate"), str(d / "probe.cpp")
-    open(probe, "w").write("int main() { return 0; }\n")
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"]
-    if subprocess.call([cxx] + san + ["-o", str(d / "probe"), probe], stderr=subprocess.DEVNULL) != 0 or subprocess.call([str(d / "probe")]) != 0:
-        san = []
-        print("jpeg_decode_emulate: the host compiler cannot link -fsanitize=address,undefined; built plain")
-    subprocess.check_call([cxx, "-O1", "-std=c++17", "-ffp-contract=off"] + san + ["-o", exe, os.path.join(HERE, "jpeg_decode_emulate.cpp")])
-
-    def run(items, dtype=np.uint8, guard=8, mangle=None, most=None):
-        images, status = [None] * len(items), [0] * len(items)
-        for (H, W, sub), idx in JD.groups(items):
-            seg, image_seg, copies, nbytes, top = JD.tables(items, idx)
-            seg = seg if mangle is None else mangle([tuple(r) for r in seg.tolist()])
-            payload = bytearray(nbytes)
-            for at, piece in copies:
-                payload[at:at + len(piece)] = piece
-            job, out = str(d / "job.bin"), str(d / "out.bin")
-            with open(job, "wb") as fp:
-                fp.write(struct.pack("<8iq", len(idx), H, W, sub, 0 if dtype == np.uint8 else 1, len(seg), top if most is None else most, guard, nbytes))
-                fp.write(np.array(seg, dtype=np.int64).tobytes() + np.array(image_seg, dtype=np.int32).tobytes() + b"".join(items[i].tables for i in idx)
-                         + bytes(payload))
-            subprocess.check_call([exe, job, out], timeout=300)          # (a loop that does not end is a failure here, not a hang)
-            raw = open(out, "rb").read()
-            B, n = len(idx), 3 * H * W
-            words = np.frombuffer(raw[:4 * B], dtype=np.uint32)
-            slots = np.frombuffer(raw[4 * B:], dtype=dtype).reshape(B, n + guard)
-            assert (slots[:, n:].view(np.uint8) == 0xA5).all()          # the guard behind every slot
-            for b, i in enumerate(idx):
-                status[i] = int(words[b])
-                images[i] = slots[b, :n].reshape(3, H, W)
-        return images, status
-
-    return run
+    """run(items, dtype, guard, mangle, most) -> (images [3, H, W] numpy, status), under the sanitizers."""
+    return D.build_emulator(tmp_path_factory.mktemp("jpeg_decode_emulate"), sanitize=True)
 
 
 def test_parse_walks_the_markers_and_refuses_on_the_host(own):

@@ -1,12 +1,10 @@
 """No GPU: include/gp_jpeg_sync.h against the binding's table; the self-synchronising entropy stage's workgroup programs
 (csrc/jpeg_sync_core.h) run lane by lane on the CPU (tests/jpeg_sync_emulate.cpp, a program of its own under
--fsanitize=address,undefined where the host compiler can link that) over every case of tests/jpeg_sync_cases.py.  The oracles: Pillow's
+the sanitizers where the host compiler can link them) over every case of tests/jpeg_sync_cases.py.  The oracles: Pillow's
 decoder and tests/jpeg_decode_ref.py for the pixels, tests/jpeg_sync_ref.py -- the header's rule in Python -- for the info words.
 Every comparison is bit-exact, and no well-formed case may come back SERIAL."""
 import ctypes as C
-import os
 import re
-import struct
 import subprocess
 
 import numpy as np
@@ -18,9 +16,6 @@ import jpeg_decode_cases as D
 import jpeg_decode_ref as REF
 import jpeg_sync_cases as SC
 from gaussianprediction_amd import _lib, jpeg_decode as JD, jpeg_sync as JS
-from test_jpeg_decode_host import _compiler
-
-HERE = os.path.dirname(os.path.abspath(__file__))
 
 _SCALARS = {"int": C.c_int32, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint32_t": C.c_uint32, "gp_stream_t": _lib.Ptr}
 _POINTEES = {"void", "uint8_t", "uint32_t", "int64_t", "int32_t", "float"}
@@ -70,65 +65,19 @@ def test_eligible_is_one_segment_and_a_scan_of_some_length():
     assert [JS.eligible(it) for it in (long, short, marked)] == [True, False, False]
 
 
-def build_emulator(d, sanitize):
-    """tests/jpeg_sync_emulate.cpp built into directory d; run(items, dtype, guard) -> (images [3, H, W] numpy, status, info)."""
-    cxx = _compiler()
-    exe, probe = str(d / "jpeg_sync_emulate"), str(d / "probe.cpp")
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"] if sanitize else []
-    if san:
-        open(probe, "w").write("int main() { return 0; }\n")
-        if subprocess.call([cxx] + san + ["-o", str(d / "probe"), probe], stderr=subprocess.DEVNULL) != 0 or subprocess.call([str(d / "probe")]) != 0:
-            san = []
-            print("jpeg_sync_emulate: the host compiler cannot link -fsanitize=address,undefined; built plain")
-    subprocess.check_call([cxx, "-O1" if san else "-O2", "-std=c++17", "-ffp-contract=off"] + san + ["-o", exe, os.path.join(HERE, "jpeg_sync_emulate.cpp")], timeout=300)
-
-    def run(items, dtype=np.uint8, guard=8):
-        images, status, info = [None] * len(items), [0] * len(items), [None] * len(items)
-        for (H, W, sub), idx in JD.groups(items):
-            seg, image_seg, copies, nbytes, top = JD.tables(items, idx)
-            payload = bytearray(nbytes)
-            for at, piece in copies:
-                payload[at:at + len(piece)] = piece
-            job, out = str(d / "job.bin"), str(d / "out.bin")
-            with open(job, "wb") as fp:
-                fp.write(struct.pack("<8iq", len(idx), H, W, sub, 0 if dtype == np.uint8 else 1, len(seg), top, guard, nbytes))
-                fp.write(np.array(seg, dtype=np.int64).tobytes() + np.array(image_seg, dtype=np.int32).tobytes() + b"".join(items[i].tables for i in idx)
-                         + bytes(payload))
-            subprocess.check_call([exe, job, out], timeout=300)          # (a loop that does not end is a failure here, not a hang)
-            raw = open(out, "rb").read()
-            B, n = len(idx), 3 * H * W
-            words = np.frombuffer(raw[:4 * B], dtype=np.uint32)
-            infos = np.frombuffer(raw[4 * B:20 * B], dtype=np.uint32).reshape(B, 4)
-            slots = np.frombuffer(raw[20 * B:], dtype=dtype).reshape(B, n + guard)
-            assert (slots[:, n:].view(np.uint8) == 0xA5).all()          # the guard behind every slot
-            for b, i in enumerate(idx):
-                status[i], info[i], images[i] = int(words[b]), tuple(int(v) for v in infos[b]), slots[b, :n].reshape(3, H, W)
-        return images, status, info
-
-    return run
-
-
 @pytest.fixture(scope="module")
 def emulator(tmp_path_factory):
-    return build_emulator(tmp_path_factory.mktemp("jpeg_sync_emulate"), sanitize=True)
+    return SC.build_emulator(tmp_path_factory.mktemp("jpeg_sync_emulate"), sanitize=True)
 
 
 @pytest.fixture(scope="module")
 def one_lane(tmp_path_factory):
     """run(item) -> (image, the GP_JPEG_DECODE_* word): csrc/jpeg_decode_core.h's one-lane program on the same single segment."""
-    d = tmp_path_factory.mktemp("jpeg_decode_emulate")
-    exe = str(d / "one_lane")
-    subprocess.check_call([_compiler(), "-O1", "-std=c++17", "-ffp-contract=off", "-o", exe, os.path.join(HERE, "jpeg_decode_emulate.cpp")], timeout=300)
+    decode = D.build_emulator(tmp_path_factory.mktemp("jpeg_decode_emulate"), sanitize=False)
 
     def run(item):
-        seg, image_seg, copies, nbytes, top = JD.tables([item], [0])
-        job, out = str(d / "job.bin"), str(d / "out.bin")
-        with open(job, "wb") as fp:
-            fp.write(struct.pack("<8iq", 1, item.H, item.W, item.sub, 0, 1, 1, 0, nbytes))
-            fp.write(np.array(seg, dtype=np.int64).tobytes() + np.array(image_seg, dtype=np.int32).tobytes() + item.tables + bytes(copies[0][1]))
-        subprocess.check_call([exe, job, out], timeout=120)
-        raw = open(out, "rb").read()
-        return np.frombuffer(raw[4:], dtype=np.uint8).reshape(3, item.H, item.W), struct.unpack("<I", raw[:4])[0]
+        (image,), (word,) = decode([item], guard=0)
+        return image, word
 
     return run
 

@@ -1,12 +1,10 @@
 """No GPU: include/gp_png_decode.h against the binding's table; the refusals that need no device; the PNG decoder's workgroup programs
-(csrc/png_decode_core.h) run lane by lane on the CPU (tests/png_decode_emulate.cpp, under -fsanitize=address,undefined where the host
-compiler can link that) over every case of tests/png_decode_cases.py, with Pillow's decoder as the oracle for the pixels and zlib's
+(csrc/png_decode_core.h) run lane by lane on the CPU (tests/png_decode_emulate.cpp, under the sanitizers where the host compiler
+can link them) over every case of tests/png_decode_cases.py, with Pillow's decoder as the oracle for the pixels and zlib's
 for what a well-formed and a malformed stream is.  Every comparison is bit-exact."""
 import ctypes as C
 import io
-import os
 import re
-import shutil
 import struct
 import subprocess
 import zlib
@@ -16,11 +14,10 @@ import pytest
 import torch
 
 import abi_check
+import emulate_build
 import png_cases as P
 import png_decode_cases as D
 from gaussianprediction_amd import _lib, png_decode as PD
-
-HERE = os.path.dirname(os.path.abspath(__file__))
 
 _SCALARS = {"int": C.c_int32, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint32_t": C.c_uint32, "gp_stream_t": _lib.Ptr}
 _POINTEES = {"void", "uint8_t", "uint32_t", "int64_t", "int32_t", "float"}
@@ -121,24 +118,11 @@ def test_checked_before_the_device_and_before_any_launch(monkeypatch, tmp_path):
 
 
 # ---- the workgroup programs on the CPU ----
-def _compiler():
-    cxx = next((c for c in (os.environ.get("CXX"), shutil.which("c++"), shutil.which("g++"), shutil.which("clang++"),
-                            "/opt/rocm/lib/llvm/bin/clang++", "/opt/rocm/llvm/bin/clang++") if c and (os.path.sep not in c or os.path.exists(c))), None)
-    assert cxx, "no host C++ compiler"
-    return cxx
-
-
 @pytest.fixture(scope="module")
 def emulator(tmp_path_factory):
     """run(items, banded, dtype, channels, bg, guard) -> (images [C_out, H, W] numpy, status, modes), one process per shape group."""
-    cxx, d = _compiler(), tmp_path_factory.mktemp("png_decode_emulate")
-    exe, probe = str(d / "png_decode_emulate"), str(d / "probe.cpp")
-    open(probe, "w").write("int main() { return 0; }\n")
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"]
-    if subprocess.call([cxx] + san + ["-o", str(d / "probe"), probe], stderr=subprocess.DEVNULL) != 0 or subprocess.call([str(d / "probe")]) != 0:
-        san = []
-        print("png_decode_emulate: the host compiler cannot link -fsanitize=address,undefined; built plain")
-    subprocess.check_call([cxx, "-O1", "-std=c++17", "-ffp-contract=off"] + san + ["-o", exe, os.path.join(HERE, "png_decode_emulate.cpp")])
+    d = tmp_path_factory.mktemp("png_decode_emulate")
+    exe = emulate_build.build("png_decode_emulate", d, sanitize=True)
 
     def run(items, banded, dtype=np.uint8, channels=None, bg=None, guard=8, mangle=None):
         images, status, modes = [None] * len(items), [0] * len(items), [0] * len(items)
@@ -230,14 +214,8 @@ def test_emulated_decoder_on_pillows_files(emulator):
 def test_emulated_decoder_on_this_projects_files(emulator, tmp_path):
     """The encoder's workgroup programs write the files (tests/png_emulate.cpp): every one with more than one band must decode BANDED
     -- the serial pass behind decode() would otherwise hide a broken fast path."""
-    exe = str(tmp_path / "png_emulate")
-    subprocess.check_call([_compiler(), "-O2", "-std=c++17", "-ffp-contract=off", "-o", exe, os.path.join(HERE, "png_emulate.cpp")])
-    cases = []
-    for name, img, fnone in D.own_inputs():
-        src, out = str(tmp_path / "in.raw"), str(tmp_path / "out.png")
-        np.ascontiguousarray(img).tofile(src)
-        subprocess.check_call([exe, str(img.shape[1]), str(img.shape[2]), "1" if img.dtype == np.uint8 else "0", "1" if fnone else "0", src, out], timeout=60)
-        cases.append(D.own_case(name, open(out, "rb").read(), img))
+    encode = P.build_emulator(tmp_path)
+    cases = [D.own_case(name, encode(img, fnone), img) for name, img, fnone in D.own_inputs()]
     assert sum(c.mode == D.BANDED for c in cases) >= 5
     items = [PD.parse(c.file) for c in cases]
     images, status, modes = emulator(items, [it.banded for it in items])          # ONE pass: no serial pass behind it

@@ -4,8 +4,6 @@ against its formula; slerp / interpolation_pose against the reference's own resu
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 import threading
 from types import SimpleNamespace
 
@@ -92,22 +90,7 @@ def test_shape_and_dtype_are_checked_before_the_device_and_any_launch(monkeypatc
 # ---- the workgroup programs on the CPU ----
 @pytest.fixture(scope="module")
 def emulator(tmp_path_factory):
-    cxx = next((c for c in (os.environ.get("CXX"), shutil.which("c++"), shutil.which("g++"), shutil.which("clang++"),
-                            "/opt/rocm/lib/llvm/bin/clang++", "/opt/rocm/llvm/bin/clang++") if c and (os.path.sep not in c or os.path.exists(c))), None)
-    assert cxx, "no host C++ compiler"
-    d = tmp_path_factory.mktemp("png_emulate")
-    exe = str(d / "png_emulate")
-    subprocess.check_call([cxx, "-O2", "-std=c++17", "-ffp-contract=off", "-o", exe, os.path.join(HERE, "png_emulate.cpp")])
-
-    def run(img, filter_none):
-        src, out = str(d / "in.raw"), str(d / "out.png")
-        np.ascontiguousarray(img).tofile(src)
-        _, H, W = img.shape
-        subprocess.check_call([exe, str(H), str(W), "1" if img.dtype == np.uint8 else "0", "1" if filter_none else "0", src, out],
-                              timeout=60)          # (a phase that does not end is a failure here, not a hang)
-        return open(out, "rb").read()
-
-    return run
+    return P.build_emulator(tmp_path_factory.mktemp("png_emulate"))
 
 
 CASES = {name: (imgs, fnone) for name, imgs, fnone in P.cases(PNG.BAND_BYTES)}

@@ -1,13 +1,9 @@
-"""No GPU: include/ext/gp_resize.h against the binding's table (an unregistered one: _lib.ABIS keeps its ten); gp_resize_coeffs against
-the numpy restatement tests/resize_ref.py; that restatement against Pillow itself; the kernels' programs (csrc/resize_core.h) run lane
-by lane on the CPU (tests/resize_emulate.cpp, under -fsanitize=address,undefined where the host compiler can link that) against Pillow;
-the refusals that need no device.  Every comparison is bit-exact."""
-import ast
+"""No GPU: include/gp_resize.h against the binding's table; gp_resize_coeffs against the numpy restatement tests/resize_ref.py; that
+restatement against Pillow itself; the kernels' programs (csrc/resize_core.h) run lane by lane on the CPU (tests/resize_emulate.cpp,
+under the sanitizers where the host compiler can link them) against Pillow; the refusals that need no device.  Every comparison is
+bit-exact."""
 import ctypes as C
-import glob
-import os
 import re
-import shutil
 import struct
 import subprocess
 
@@ -16,11 +12,9 @@ import pytest
 import torch
 
 import abi_check
+import emulate_build
 import resize_ref as ref
 from gaussianprediction_amd import _lib, resize_ops as R
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 
 _SCALARS = {"int": C.c_int32, "int32_t": C.c_int32, "int64_t": C.c_int64, "gp_stream_t": _lib.Ptr}
 _POINTEES = {"void", "uint8_t", "int32_t"}
@@ -28,19 +22,14 @@ _POINTEES = {"void", "uint8_t", "int32_t"}
 
 def test_prototype_table_equals_the_header():
     protos = abi_check.check_table(R.ABI, 6, _SCALARS, _POINTEES)
-    assert R.ABI.prototypes is R.PROTOTYPES and R.ABI.header == "ext/gp_resize.h"
+    assert R.ABI.prototypes is R.PROTOTYPES and R.ABI.header == "gp_resize.h"
     assert protos["gp_resize_u8"][1][-1] == "gp_stream_t"          # the stream is the last parameter
 
 
-def test_table_is_applied_and_stays_unregistered():
-    from gaussianprediction_amd import (densify_ops, gcn_ops, jpeg_decode, jpeg_ops, jpeg_sync, kmeans_ops, lpips, metrics,  # noqa: F401
-                                        png_decode, png_ops)
-    abi_check.check_applied(R.ABI)
-    assert len(_lib.ABIS) == 10 and R.ABI not in _lib.ABIS
-    assert sorted(a.header for a in _lib.ABIS) == sorted(f for f in os.listdir(os.path.join(ROOT, "include")) if f.endswith(".h"))
-    assert not set(R.PROTOTYPES) & {n for a in _lib.ABIS for n in a.prototypes}
-    defs = {k: int(v) for k, v in re.findall(r"#define (GP_RESIZE_[A-Z0-9_]+) (\d+)\b", abi_check.header_text("ext/gp_resize.h"))}
+def test_symbols_and_constants():
+    defs = {k: int(v) for k, v in re.findall(r"#define (GP_RESIZE_[A-Z0-9_]+) (\d+)\b", abi_check.header_text("gp_resize.h"))}
     assert defs["GP_RESIZE_ABI_VERSION"] == R.GP_RESIZE_ABI_VERSION == R.ABI.version == 1
+    abi_check.check_applied(R.ABI)
     assert {k: defs["GP_RESIZE_" + k.upper()] for k in R.FILTERS} == R.FILTERS == ref.FILTERS
     from PIL import Image
     assert {k: int(getattr(Image.Resampling, k.upper())) for k in R.FILTERS} == R.FILTERS
@@ -48,25 +37,6 @@ def test_table_is_applied_and_stays_unregistered():
     assert [defs["GP_RESIZE_PATH_" + k] for k in ("COPY", "FUSED", "TWO_LAUNCH", "HORIZONTAL", "VERTICAL")] == \
         [R.PATH_COPY, R.PATH_FUSED, R.PATH_TWO_LAUNCH, R.PATH_HORIZONTAL, R.PATH_VERTICAL] == list(range(5))
     assert (defs["GP_RESIZE_TILE_W"], defs["GP_RESIZE_TILE_H"]) == (R.TILE_W, R.TILE_H)
-
-
-def test_every_call_site_of_this_table_passes_as_many_arguments_as_the_prototype_has():
-    """The audit of tests/test_host_and_abi.py walks the registered tables only; the same walk for this one."""
-    want = {name: len(argtypes) for name, (_, argtypes) in R.PROTOTYPES.items()}
-    files = [p for d in ("gaussianprediction_amd", "tools", "tests") for p in glob.glob(os.path.join(ROOT, d, "**", "*.py"), recursive=True)]
-    seen = {name: 0 for name in want}
-    for path in sorted(files):
-        for node in ast.walk(ast.parse(open(path).read(), path)):
-            if not isinstance(node, ast.Call):
-                continue
-            f, args, keywords = node.func, node.args, node.keywords
-            name = f.attr if isinstance(f, ast.Attribute) else None
-            if name == "scratch" and args and isinstance(args[0], ast.Attribute):           # _lib.scratch(query, *args, device=...)
-                name, args, keywords = args[0].attr, args[1:], []
-            if name in want and not any(isinstance(a, ast.Starred) for a in args):
-                assert not keywords and len(args) == want[name], (os.path.relpath(path, ROOT), node.lineno, name)
-                seen[name] += 1
-    assert all(seen[n] for n in want if n != "gp_resize_abi_version"), seen
 
 
 PAIRS = [(i, o) for i in range(1, 41) for o in range(1, 41)] + [(1352, 676), (1014, 507), (135, 67), (600, 9), (9, 600)]
@@ -126,24 +96,11 @@ def test_default_filter_and_copy_are_pillows():
 
 
 # ---- the kernels' programs on the CPU ----
-def _compiler():
-    cxx = next((c for c in (os.environ.get("CXX"), shutil.which("c++"), shutil.which("g++"), shutil.which("clang++"),
-                            "/opt/rocm/lib/llvm/bin/clang++", "/opt/rocm/llvm/bin/clang++") if c and (os.path.sep not in c or os.path.exists(c))), None)
-    assert cxx, "no host C++ compiler"
-    return cxx
-
-
 @pytest.fixture(scope="module")
 def emulator(tmp_path_factory):
     """run(batch uint8 [B, C, H, W], size, name, alpha, dtype, src_gap, guard) -> (path, [B, C, Ho, Wo] numpy)."""
-    cxx, d = _compiler(), tmp_path_factory.mktemp("resize_emulate")
-    exe, probe = str(d / "resize_emulate"), str(d / "probe.cpp")
-    open(probe, "w").write("int main() { return 0; }\n")
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"]
-    if subprocess.call([cxx] + san + ["-o", str(d / "probe"), probe], stderr=subprocess.DEVNULL) != 0 or subprocess.call([str(d / "probe")]) != 0:
-        san = []
-        print("resize_emulate: the host compiler cannot link -fsanitize=address,undefined; built plain")
-    subprocess.check_call([cxx, "-O1", "-std=c++17", "-ffp-contract=off"] + san + ["-o", exe, os.path.join(HERE, "resize_emulate.cpp")])
+    d = tmp_path_factory.mktemp("resize_emulate")
+    exe = emulate_build.build("resize_emulate", d, sanitize=True)
 
     def run(batch, size, name="bicubic", alpha=None, dtype=np.uint8, src_gap=0, guard=8):
         B, Cn, H, W = batch.shape

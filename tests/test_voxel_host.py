@@ -1,13 +1,9 @@
-"""No GPU: include/ext/gp_voxel.h against the binding's table (an unregistered one: _lib.ABIS keeps its ten); gp_voxel_downsample_host --
-the programs of csrc/voxel_core.h on the CPU -- against the numpy restatement tests/voxel_ref.py; the same programs in a stand-alone
-build (tests/voxel_emulate.cpp, under -fsanitize=address,undefined where the host compiler can link that); the refusals that need no
-device; the loop's voxel sizes; the PLY writer.  Every comparison is bit-exact."""
-import ast
+"""No GPU: include/gp_voxel.h against the binding's table; gp_voxel_downsample_host -- the programs of csrc/voxel_core.h on the CPU --
+against the numpy restatement tests/voxel_ref.py; the same programs in a stand-alone build (tests/voxel_emulate.cpp, under the
+sanitizers where the host compiler can link them); the refusals that need no device; the loop's voxel sizes; the PLY writer.  Every
+comparison is bit-exact."""
 import ctypes as C
-import glob
-import os
 import re
-import shutil
 import struct
 import subprocess
 
@@ -16,11 +12,9 @@ import pytest
 import torch
 
 import abi_check
+import emulate_build
 import voxel_ref as ref
 from gaussianprediction_amd import _lib, io_formats, voxel_ops as V
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 
 _SCALARS = {"int": C.c_int32, "int32_t": C.c_int32, "int64_t": C.c_int64, "double": C.c_double, "gp_stream_t": _lib.Ptr}
 _POINTEES = {"void", "double", "int32_t", "int64_t"}
@@ -45,40 +39,17 @@ def check_pass(got, points, voxel_size, colors, normals):
 
 def test_prototype_table_equals_the_header():
     protos = abi_check.check_table(V.ABI, 5, _SCALARS, _POINTEES)
-    assert V.ABI.prototypes is V.PROTOTYPES and V.ABI.header == "ext/gp_voxel.h"
+    assert V.ABI.prototypes is V.PROTOTYPES and V.ABI.header == "gp_voxel.h"
     for name in ("gp_voxel_bounds", "gp_voxel_downsample"):
         assert protos[name][1][-1] == "gp_stream_t"              # the stream is the last parameter
     assert "gp_stream_t" not in protos["gp_voxel_downsample_host"][1]
 
 
-def test_table_is_applied_and_stays_unregistered():
-    from gaussianprediction_amd import (densify_ops, gcn_ops, jpeg_decode, jpeg_ops, jpeg_sync, kmeans_ops, lpips, metrics,  # noqa: F401
-                                        png_decode, png_ops)
-    abi_check.check_applied(V.ABI)
-    assert len(_lib.ABIS) == 10 and V.ABI not in _lib.ABIS
-    assert sorted(a.header for a in _lib.ABIS) == sorted(f for f in os.listdir(os.path.join(ROOT, "include")) if f.endswith(".h"))
-    assert not set(V.PROTOTYPES) & {n for a in _lib.ABIS for n in a.prototypes}
-    defs = {k: int(v) for k, v in re.findall(r"#define (GP_VOXEL_[A-Z0-9_]+) (\d+)\b", abi_check.header_text("ext/gp_voxel.h"))}
+def test_symbols_and_constants():
+    defs = {k: int(v) for k, v in re.findall(r"#define (GP_VOXEL_[A-Z0-9_]+) (\d+)\b", abi_check.header_text("gp_voxel.h"))}
     assert defs["GP_VOXEL_ABI_VERSION"] == V.GP_VOXEL_ABI_VERSION == V.ABI.version == 1
+    abi_check.check_applied(V.ABI)
     assert defs["GP_VOXEL_RECORD_DOUBLES"] == V.RECORD_DOUBLES == 8
-
-
-def test_every_call_site_of_this_table_passes_as_many_arguments_as_the_prototype_has():
-    want = {name: len(argtypes) for name, (_, argtypes) in V.PROTOTYPES.items()}
-    files = [p for d in ("gaussianprediction_amd", "tools", "tests") for p in glob.glob(os.path.join(ROOT, d, "**", "*.py"), recursive=True)]
-    seen = {name: 0 for name in want}
-    for path in sorted(files):
-        for node in ast.walk(ast.parse(open(path).read(), path)):
-            if not isinstance(node, ast.Call):
-                continue
-            f, args, keywords = node.func, node.args, node.keywords
-            name = f.attr if isinstance(f, ast.Attribute) else None
-            if name == "scratch" and args and isinstance(args[0], ast.Attribute):           # _lib.scratch(query, *args, device=...)
-                name, args, keywords = args[0].attr, args[1:], []
-            if name in want and not any(isinstance(a, ast.Starred) for a in args):
-                assert not keywords and len(args) == want[name], (os.path.relpath(path, ROOT), node.lineno, name)
-                seen[name] += 1
-    assert all(seen[n] for n in want if n != "gp_voxel_abi_version"), seen
 
 
 def test_the_restatement_sums_in_ascending_input_row():
@@ -229,24 +200,11 @@ def test_ply_round_trip_and_colour_bytes(tmp_path):
 
 
 # ---- the programs in a stand-alone build, under the sanitizers ----
-def _compiler():
-    cxx = next((c for c in (os.environ.get("CXX"), shutil.which("c++"), shutil.which("g++"), shutil.which("clang++"),
-                            "/opt/rocm/lib/llvm/bin/clang++", "/opt/rocm/llvm/bin/clang++") if c and (os.path.sep not in c or os.path.exists(c))), None)
-    assert cxx, "no host C++ compiler"
-    return cxx
-
-
 @pytest.fixture(scope="module")
 def emulator(tmp_path_factory):
     """run(points, voxel_size, colors, normals) -> (points, colors, normals, index), or the refusal's code as an int."""
-    cxx, d = _compiler(), tmp_path_factory.mktemp("voxel_emulate")
-    exe, probe = str(d / "voxel_emulate"), str(d / "probe.cpp")
-    open(probe, "w").write("int main() { return 0; }\n")
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"]
-    if subprocess.call([cxx] + san + ["-o", str(d / "probe"), probe], stderr=subprocess.DEVNULL) != 0 or subprocess.call([str(d / "probe")]) != 0:
-        san = []
-        print("voxel_emulate: the host compiler cannot link -fsanitize=address,undefined; built plain")
-    subprocess.check_call([cxx, "-O1", "-std=c++17", "-ffp-contract=off"] + san + ["-o", exe, os.path.join(HERE, "voxel_emulate.cpp")])
+    d = tmp_path_factory.mktemp("voxel_emulate")
+    exe = emulate_build.build("voxel_emulate", d, sanitize=True)
 
     def run(points, voxel_size, colors=None, normals=None):
         n = len(points)

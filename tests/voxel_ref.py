@@ -1,4 +1,4 @@
-"""The voxel-grid downsample of include/ext/gp_voxel.h restated in numpy float64, and the clouds the host and the device tests share.
+"""The voxel-grid downsample of include/gp_voxel.h restated in numpy float64, and the clouds the host and the device tests share.
 
 The formulae are Open3D's PointCloud::VoxelDownSample as its published source states them (Open3D itself is not installed where this
 was written, so nothing here is pinned against its binary): min_bound = min - voxel_size / 2, index = floor((p - min_bound) /

@@ -1,4 +1,4 @@
-"""On-device image resizing (resize_ops / include/ext/gp_resize.h) measured on the GPU against Pillow on this host: the workload's
+"""On-device image resizing (resize_ops / include/gp_resize.h) measured on the GPU against Pillow on this host: the workload's
 shape, 1352 x 1014 -> 676 x 507 RGB with the bicubic filter, B = 1 and B = 16, uint8 and float32 output, hipEvent-timed, the result
 checked against Pillow's bytes first; an RGBA batch (premultiplied alpha); the single-pass and the two-launch paths for comparison;
 and Pillow's Image.resize of the same images with one thread and with a pool of 16.  Writes profiles/resize_probe.txt.

@@ -1,4 +1,4 @@
-"""Voxel-grid downsampling on the device (voxel_ops / include/ext/gp_voxel.h) measured on the GPU against the numpy restatement of the
+"""Voxel-grid downsampling on the device (voxel_ops / include/gp_voxel.h) measured on the GPU against the numpy restatement of the
 same formulae (tests/voxel_ref.py) on this host -- not against Open3D, which is not installed: the reference's loop (voxel 0.02, + 0.01
 a pass, until at most 40 000 points) on a synthetic surface cloud of 1 M coloured points, and the single pass at voxel 0.02, with the
 library's brackets around each group of launches.  Both results are first compared bit for bit.  Writes profiles/voxel_probe.txt.
