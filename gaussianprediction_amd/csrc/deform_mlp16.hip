@@ -1891,9 +1891,9 @@ extern "C" int gp_mlp16_backward(const gp_mlp16_params* p /* w16 = TRANSPOSED co
     };
     if (m.rows >= 4096) {       // LDS-staged kernel: grid = (row slabs, jobs), three launches cover the five layers
         const long n_kb = (m.rows + 63) / 64 * (64 / T16_BLK);   // 16-row blocks incl. the zero padding to 64 rows
-        // 4096-row slabs: every slab ends in 64 k atomic adds per (layer, term), and below that size they show (round 5, tools/probe/
-        // mlp16_wgrad_slabs.py at 200 k rows: 1024-row slabs 0.72 ms, 4096-row slabs 0.59; 1 M rows sat at the 256-slab cap = 4096 rows already)
-        const int slab_kb = gp_debug_get(10) > 0 ? gp_debug_get(10) : 256;    // (gp_debug_option(10, n): n 16-row blocks per slab)
+        // 4096-row slabs: every slab ends in 64 k atomic adds per (layer, term), and below that size they show (round 5, profiles/
+        // r05_mlp16_wgrad_slabs.txt at 200 k rows: 1024-row slabs 0.72 ms, 4096-row slabs 0.59; 1 M rows sat at the 256-slab cap = 4096 rows already)
+        const int slab_kb = 256;                                  // 16-row blocks per slab
         long nslab = n_kb / slab_kb;
         const long few = n_kb / 16 < 32 ? n_kb / 16 : 32;        // ... but at least 32 slabs of >= 256 rows at small row counts
         if (nslab < few) nslab = few;
@@ -1907,7 +1907,7 @@ extern "C" int gp_mlp16_backward(const gp_mlp16_params* p /* w16 = TRANSPOSED co
             first.j[t] = term(opnd(0), t, g->dw[0], g->db[0]);
             last.j[t] = term(opnd(4), t, g->dw[4], g->db[4]);
         }
-        const int xt = (split && gp_debug_get(3) == 0) ? n_terms : 0;      // (gp_debug_option(3, 1): the round-2 2-D grid, for A/B)
+        const int xt = split ? n_terms : 0;       // (0: the round-2 2-D grid of jobs x slabs, which fp16 and bf16 ship on)
         const W16Shape sh_mid{256, 256, 256, 256, 256, NS * 256, NS * 256, split, xt, 3 * n_terms, (int)gx},
             sh_first{256, m.in_pad, 256, m.in_dim, m.in_dim, NS * 256, NS * m.in_pad, split, xt, n_terms, (int)gx},
             sh_last{16, 256, m.out_dim, 256, 256, NS * 16, NS * 256, split, xt, n_terms, (int)gx};

@@ -416,13 +416,7 @@ int gp_raster_backward_impl(const gp_raster_settings* st, const gp_raster_inputs
         static thread_local int ablate_set = 0;
         if (gp_debug_get(1) != ablate_set) { ablate_set = gp_debug_get(1); if (gp_bwd_set_ablate(ablate_set)) GP_FAIL("bwd ablate flag"); }
         GpProfScope _p("composite_bwd", s);
-        // gp_debug_option(7, v): 0 = the quadrant kernel (shipped); 3 = the sub-block kernel of round 5 (4x4 culling: 1.5 evaluated pairs
-        // per contributing one instead of 3.0, and slower -- raster_kernels.hip), 2 = its counting variant
-        // (g_pair_counters[2], [3]).  The sub-block kernel packs four bits above the Gaussian id: N < GP_BWD_SB_MAX_N.
-        const int variant = gp_debug_get(7);
         auto kern = dL_ddepth ? gp_composite_bwd_depth_kernel : gp_composite_bwd_kernel;
-        if (variant == 3 && N < (size_t)GP_BWD_SB_MAX_N) kern = dL_ddepth ? gp_composite_bwd_sb_depth_kernel : gp_composite_bwd_sb_kernel;
-        else if (variant == 2 && !dL_ddepth && N < (size_t)GP_BWD_SB_MAX_N) kern = gp_composite_bwd_sb_count_kernel;
         hipLaunchKernelGGL(kern, dim3((unsigned)((T + 7) / 8 * 8) * GP_BWD_PARTS),
                            dim3(64), 0, s, d, il.ranges, point_list, (const uint16_t*)((const uint8_t*)point_list + gp_align_up((size_t)R * 4, 256)), gl.rec,
                            st->bg, (const float*)fwd->color, (const float*)fwd->depth, (const float*)il.final_T,

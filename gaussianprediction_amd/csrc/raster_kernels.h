@@ -40,12 +40,15 @@ struct RasterDims {
 __global__ __launch_bounds__(256) void gp_key_range_kernel(const uint32_t* __restrict__ keys, const int32_t* __restrict__ radii, int n,
                                                           uint32_t base, uint32_t* __restrict__ out2);
 
-__global__ __launch_bounds__(256) void gp_preprocess_fwd_kernel(RasterDims d, const float* __restrict__ means3D, const float* __restrict__ scales,      const float* __restrict__ rotations, const float* __restrict__ opacities, const float* __restrict__ shs,      const float* __restrict__ shs_rest, const float* __restrict__ colors_precomp, const float* __restrict__ cov3D_precomp,      const float* __restrict__ view, const float* __restrict__ proj, const float* __restrict__ campos,      int32_t* __restrict__ radii, float4* __restrict__ rec, uint32_t* __restrict__ depth_key,      uint2* __restrict__ tiles_touched, uint8_t* __restrict__ clamped);
-
-__global__ __launch_bounds__(256) void gp_preprocess_fwd_sh16_kernel(RasterDims d, const float* __restrict__ means3D, const float* __restrict__ scales,      const float* __restrict__ rotations, const float* __restrict__ opacities, const float* __restrict__ shs,      const float* __restrict__ shs_rest, const float* __restrict__ colors_precomp, const float* __restrict__ cov3D_precomp,      const float* __restrict__ view, const float* __restrict__ proj, const float* __restrict__ campos,      int32_t* __restrict__ radii, float4* __restrict__ rec, uint32_t* __restrict__ depth_key,      uint2* __restrict__ tiles_touched, uint8_t* __restrict__ clamped);
-
-__global__ __launch_bounds__(256) void gp_preprocess_fwd_split_kernel(RasterDims d, const float* __restrict__ means3D, const float* __restrict__ scales,      const float* __restrict__ rotations, const float* __restrict__ opacities, const float* __restrict__ shs,      const float* __restrict__ shs_rest, const float* __restrict__ colors_precomp, const float* __restrict__ cov3D_precomp,      const float* __restrict__ view, const float* __restrict__ proj, const float* __restrict__ campos,      int32_t* __restrict__ radii, float4* __restrict__ rec, uint32_t* __restrict__ depth_key,      uint2* __restrict__ tiles_touched, uint8_t* __restrict__ clamped);
-
+#define GP_PF_ARGS RasterDims d, const float* __restrict__ means3D, const float* __restrict__ scales, \
+    const float* __restrict__ rotations, const float* __restrict__ opacities, const float* __restrict__ shs, \
+    const float* __restrict__ shs_rest, const float* __restrict__ colors_precomp, const float* __restrict__ cov3D_precomp, \
+    const float* __restrict__ view, const float* __restrict__ proj, const float* __restrict__ campos, \
+    int32_t* __restrict__ radii, float4* __restrict__ rec, uint32_t* __restrict__ depth_key, \
+    uint2* __restrict__ tiles_touched, uint8_t* __restrict__ clamped
+__global__ __launch_bounds__(256) void gp_preprocess_fwd_kernel(GP_PF_ARGS);
+__global__ __launch_bounds__(256) void gp_preprocess_fwd_sh16_kernel(GP_PF_ARGS);
+__global__ __launch_bounds__(256) void gp_preprocess_fwd_split_kernel(GP_PF_ARGS);
 #define GP_SC_ARGS RasterDims d, const float* __restrict__ means3D, const float* __restrict__ shs, const float* __restrict__ shs_rest, \
     const float* __restrict__ campos, const int32_t* __restrict__ radii, float4* __restrict__ rec, uint8_t* __restrict__ clamped
 __global__ __launch_bounds__(256) void gp_sh_color_kernel(GP_SC_ARGS);
@@ -71,24 +74,26 @@ __global__ __launch_bounds__(1024) void gp_tile_order_kernel(const int2* __restr
 __global__ __launch_bounds__(1024) void gp_bwd_prologue_kernel(const int2* __restrict__ ranges, const int32_t* __restrict__ work_hint, int T,
                                                                uint32_t* __restrict__ order, float* __restrict__ acc, size_t acc_floats);
 
+#define GP_PB_ARGS RasterDims d, const float* __restrict__ means3D, const float* __restrict__ scales, \
+    const float* __restrict__ rotations, const float* __restrict__ shs, const float* __restrict__ shs_rest, \
+    const float* __restrict__ cov3D_precomp, const float* __restrict__ view, const float* __restrict__ proj, \
+    const float* __restrict__ campos, const int32_t* __restrict__ radii, const uint8_t* __restrict__ clamped, \
+    const float* __restrict__ g_mean2D, const float* __restrict__ g_conic, const float* __restrict__ g_opacity, \
+    const float* __restrict__ g_color, const float* __restrict__ g_depth, float* __restrict__ dL_dmeans3D, \
+    float* __restrict__ dL_dmeans2D, float* __restrict__ dL_dshs, float* __restrict__ dL_dshs_rest, \
+    float* __restrict__ dL_dcolors, float* __restrict__ dL_dopacities, float* __restrict__ dL_dscales, \
+    float* __restrict__ dL_drots, float* __restrict__ dL_dcov3D, int accumulate_shs, AdamFuseDev af
+__global__ __launch_bounds__(256) void gp_preprocess_bwd_kernel(GP_PB_ARGS);
+__global__ __launch_bounds__(256) void gp_preprocess_bwd_sh16_kernel(GP_PB_ARGS);
+__global__ __launch_bounds__(256) void gp_preprocess_bwd_split_kernel(GP_PB_ARGS);
 
-
-__global__ __launch_bounds__(256) void gp_preprocess_bwd_kernel(RasterDims d, const float* __restrict__ means3D, const float* __restrict__ scales,      const float* __restrict__ rotations, const float* __restrict__ shs, const float* __restrict__ shs_rest,      const float* __restrict__ cov3D_precomp, const float* __restrict__ view, const float* __restrict__ proj,      const float* __restrict__ campos, const int32_t* __restrict__ radii, const uint8_t* __restrict__ clamped,      const float* __restrict__ g_mean2D, const float* __restrict__ g_conic, const float* __restrict__ g_opacity,      const float* __restrict__ g_color, const float* __restrict__ g_depth, float* __restrict__ dL_dmeans3D,      float* __restrict__ dL_dmeans2D, float* __restrict__ dL_dshs, float* __restrict__ dL_dshs_rest,      float* __restrict__ dL_dcolors, float* __restrict__ dL_dopacities, float* __restrict__ dL_dscales,      float* __restrict__ dL_drots, float* __restrict__ dL_dcov3D, int accumulate_shs, AdamFuseDev af);
-
-__global__ __launch_bounds__(256) void gp_preprocess_bwd_sh16_kernel(RasterDims d, const float* __restrict__ means3D, const float* __restrict__ scales,      const float* __restrict__ rotations, const float* __restrict__ shs, const float* __restrict__ shs_rest,      const float* __restrict__ cov3D_precomp, const float* __restrict__ view, const float* __restrict__ proj,      const float* __restrict__ campos, const int32_t* __restrict__ radii, const uint8_t* __restrict__ clamped,      const float* __restrict__ g_mean2D, const float* __restrict__ g_conic, const float* __restrict__ g_opacity,      const float* __restrict__ g_color, const float* __restrict__ g_depth, float* __restrict__ dL_dmeans3D,      float* __restrict__ dL_dmeans2D, float* __restrict__ dL_dshs, float* __restrict__ dL_dshs_rest,      float* __restrict__ dL_dcolors, float* __restrict__ dL_dopacities, float* __restrict__ dL_dscales,      float* __restrict__ dL_drots, float* __restrict__ dL_dcov3D, int accumulate_shs, AdamFuseDev af);
-
-__global__ __launch_bounds__(256) void gp_preprocess_bwd_split_kernel(RasterDims d, const float* __restrict__ means3D, const float* __restrict__ scales,      const float* __restrict__ rotations, const float* __restrict__ shs, const float* __restrict__ shs_rest,      const float* __restrict__ cov3D_precomp, const float* __restrict__ view, const float* __restrict__ proj,      const float* __restrict__ campos, const int32_t* __restrict__ radii, const uint8_t* __restrict__ clamped,      const float* __restrict__ g_mean2D, const float* __restrict__ g_conic, const float* __restrict__ g_opacity,      const float* __restrict__ g_color, const float* __restrict__ g_depth, float* __restrict__ dL_dmeans3D,      float* __restrict__ dL_dmeans2D, float* __restrict__ dL_dshs, float* __restrict__ dL_dshs_rest,      float* __restrict__ dL_dcolors, float* __restrict__ dL_dopacities, float* __restrict__ dL_dscales,      float* __restrict__ dL_drots, float* __restrict__ dL_dcov3D, int accumulate_shs, AdamFuseDev af);
-
-
-__global__ __launch_bounds__(256) void gp_composite_fwd_sb_kernel(RasterDims d, const int2* __restrict__ ranges,
-                                                                  const uint32_t* __restrict__ point_list,
-                                                                  const float4* __restrict__ rec,
-                                                                  const float* __restrict__ bg,
-                                                                  float* __restrict__ out_color,
-                                                                  float* __restrict__ out_depth,
-                                                                  int32_t* __restrict__ out_tidx,
-                                                                  float* __restrict__ final_T,
-                                                                  int32_t* __restrict__ n_contrib, const uint32_t* __restrict__ order, int32_t* __restrict__ tile_work, uint16_t* __restrict__ smask);
+#define GP_CF_ARGS RasterDims d, const int2* __restrict__ ranges, const uint32_t* __restrict__ point_list, const float4* __restrict__ rec, \
+    const float* __restrict__ bg, float* __restrict__ out_color, float* __restrict__ out_depth, int32_t* __restrict__ out_tidx, \
+    float* __restrict__ final_T, int32_t* __restrict__ n_contrib, const uint32_t* __restrict__ order, int32_t* __restrict__ tile_work, \
+    uint16_t* __restrict__ smask
+__global__ __launch_bounds__(256) void gp_composite_fwd_sb_kernel(GP_CF_ARGS);
+__global__ __launch_bounds__(256) void gp_composite_fwd_sbc_kernel(GP_CF_ARGS);      // compiler-scheduled inner loop (gp_debug_option(0, 2))
+__global__ __launch_bounds__(256) void gp_composite_fwd_count_kernel(GP_CF_ARGS);    // ... + pair counters (gp_debug_option(0, 3))
 
 // heavy-first launch order: bucket of a tile by a 2-mantissa-bit logarithm of its work (0 = heaviest ... 127 = no work)
 __device__ __forceinline__ int gp_tile_bucket(int w) {
@@ -141,25 +146,6 @@ __device__ __forceinline__ void gp_tile_order_body256(const int2* __restrict__ r
 }
 int gp_pair_counters_read(unsigned long long* out4);
 int gp_bwd_set_ablate(int v);
-__global__ __launch_bounds__(256) void gp_composite_fwd_count_kernel(RasterDims d, const int2* __restrict__ ranges,
-                                                                  const uint32_t* __restrict__ point_list,
-                                                                  const float4* __restrict__ rec,
-                                                                  const float* __restrict__ bg,
-                                                                  float* __restrict__ out_color,
-                                                                  float* __restrict__ out_depth,
-                                                                  int32_t* __restrict__ out_tidx,
-                                                                  float* __restrict__ final_T,
-                                                                  int32_t* __restrict__ n_contrib, const uint32_t* __restrict__ order, int32_t* __restrict__ tile_work, uint16_t* __restrict__ smask);
-
-__global__ __launch_bounds__(256) void gp_composite_fwd_sbc_kernel(RasterDims d, const int2* __restrict__ ranges,
-                                                                  const uint32_t* __restrict__ point_list,
-                                                                  const float4* __restrict__ rec,
-                                                                  const float* __restrict__ bg,
-                                                                  float* __restrict__ out_color,
-                                                                  float* __restrict__ out_depth,
-                                                                  int32_t* __restrict__ out_tidx,
-                                                                  float* __restrict__ final_T,
-                                                                  int32_t* __restrict__ n_contrib, const uint32_t* __restrict__ order, int32_t* __restrict__ tile_work, uint16_t* __restrict__ smask);
 
 #define GP_CB_ARGS RasterDims d, const int2* __restrict__ ranges, const uint32_t* __restrict__ point_list, \
     const uint16_t* __restrict__ smask, const float4* __restrict__ rec, const float* __restrict__ bg, const float* __restrict__ out_color, \
@@ -168,8 +154,3 @@ __global__ __launch_bounds__(256) void gp_composite_fwd_sbc_kernel(RasterDims d,
     float* __restrict__ g_opacity, float* __restrict__ g_color, float* __restrict__ g_depth, const uint32_t* __restrict__ order
 __global__ __launch_bounds__(64) void gp_composite_bwd_kernel(GP_CB_ARGS);
 __global__ __launch_bounds__(64) void gp_composite_bwd_depth_kernel(GP_CB_ARGS);
-// round 5: 16-lane groups walk the quadrant's four 4x4 sub-blocks (an A/B variant, gp_debug_option(7, 3): measured slower than the two above)
-__global__ __launch_bounds__(64) void gp_composite_bwd_sb_kernel(GP_CB_ARGS);
-__global__ __launch_bounds__(64) void gp_composite_bwd_sb_depth_kernel(GP_CB_ARGS);
-__global__ __launch_bounds__(64) void gp_composite_bwd_sb_count_kernel(GP_CB_ARGS);
-#define GP_BWD_SB_MAX_N (1 << 28)      // the sub-block kernel packs its 4 sub-block bits above the Gaussian id

@@ -662,19 +662,27 @@ int gp_microbench_valu(int kind, int iters, float* sink, double* instr_out, gp_s
  * Bracketed as "mb_gather"; run under `rocprofv3 --pmc FETCH_SIZE` it calibrates the counter for this access shape. */
 int gp_microbench_gather(const void* src, int rec_bytes, int stride_bytes, const uint32_t* idx, size_t n_idx, float* sink,
                          gp_stream_t stream);
-/* Diagnostics: select a kernel variant for A/B profiling (key 0: composite forward, key 1: composite backward; value 0 =
- * the shipped default; key 2: access shape of gp_microbench_copy, tools/copy_peak_sweep.py; key 3: 1 = round 2's 2-D grid of the
- * split-mode weight-gradient kernel; key 4: workgroup cap of the fused weights-model forward;
- * key 5: 1 = tile binning by duplicate + radix sort instead of by counting, csrc/bin_kernels.hip; key 6: ablation bits of the
- * binning scatter kernel; key 8: 2 = depth sort in three 11-bit counting passes instead of four 8-bit radix passes -- measured slower, kept for the A/B;
- * key 9: ablation bits of the 16-bit MLP forward, tools/probe/mlp16_ablate.py; key 10: 16-row blocks per slab of the 16-bit weight gradient;
- * key 11: 1 = the pair of loss kernels in gp_train_step_run; key 12: P > 1 = gp_profile_enable(1) brackets every P-th launch only; key 13: 1 = the 16-row kernels where the feature-split small-row MLP would run,
- * 2 = its agent-scope form of the exchange; key 14: 1 = activation launches of their own in gp_train_step_run instead of raw_activations).
- * Never needed by a caller of the render path. */
+/* Diagnostics: select a kernel variant for A/B profiling.  Value 0 = the shipped default for every key; never needed by a
+ * caller of the render path.  The keys:
+ *    0  composite forward: 2 = the compiler-scheduled visit loop, 3 = that loop + the pair counters of gp_debug_counters
+ *    1  ablation bits of the composite backward
+ *    4  workgroup cap of the fused weights-model forward
+ *    5  1 = tile binning by duplicate + radix sort instead of by counting, csrc/bin_kernels.hip
+ *    6  ablation bits of the binning scatter kernel
+ *    8  2 = depth sort in three 11-bit counting passes instead of four 8-bit radix passes -- measured slower, kept for the A/B
+ *    9  ablation bits of the 16-bit MLP forward, tools/probe/mlp16_ablate.py
+ *   11  1 = the pair of loss kernels in gp_train_step_run
+ *   12  P > 1 = gp_profile_enable(1) brackets every P-th launch only
+ *   13  1 = the 16-row kernels where the feature-split small-row MLP would run, 2 = its agent-scope form of the exchange
+ *   14  1 = activation launches of their own in gp_train_step_run instead of raw_activations
+ *   15  bits 1 / 2 / 4 = gp_train_step_run launches rider A / B / C on its own instead of inside its carrier kernel
+ *   2, 3, 7, 10  retired (copy access shapes, 2-D split weight-gradient grid, sub-block composite backward, weight-gradient
+ *       slab size: measured, recorded under profiles/, removed): the call fails with "key <k> was retired" */
 int gp_debug_option(int key, int value);
 /* Diagnostics: with gp_debug_option(0, 3) the composite forward counts, over all launches since the last call, out4[0] = the
  * (pixel, splat) pairs that contribute (alpha >= 1/255, pixel not yet saturated) and out4[1] = the pairs its sub-block lists make
- * it evaluate; this call synchronises the device, returns and clears them (bench.py: roofline.contributing_pairs). */
+ * it evaluate; this call synchronises the device, returns and clears them (bench.py: roofline.contributing_pairs).
+ * out4[2] and out4[3] are always 0 (they counted for the retired sub-block backward). */
 int gp_debug_counters(uint64_t* out4);
 
 const char* gp_last_error(void);

@@ -65,6 +65,14 @@ def test_abi_validation_errors_are_reported_not_thrown():
         _lib.check(rc, "gp_mlp_forward")
 
 
+def test_retired_debug_keys_are_refused():
+    """A script that still selects a removed kernel variant fails at the call; it does not time the default in silence."""
+    l = _lib.lib()
+    for k in (2, 3, 7, 10):
+        assert l.gp_debug_option(k, 1) != 0 and b"retired" in l.gp_last_error()
+    assert l.gp_debug_option(5, 0) == 0
+
+
 def test_debug_index_entries_validate_their_arguments():
     """gp_debug_sort_pairs / gp_debug_scan_blocks / gp_debug_bin_lists refuse bad arguments before anything touches a device."""
     l = _lib.lib()
