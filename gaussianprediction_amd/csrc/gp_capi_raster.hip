@@ -429,13 +429,15 @@ int gp_raster_backward_impl(const gp_raster_settings* st, const gp_raster_inputs
         auto kern = gp_preprocess_bwd_kernel;
         if (in->shs && in->shs_rest) {
             if (!al16 || (!g->dL_dshs_rest && !af.on)) GP_FAIL("split SH mode needs 16-byte aligned tensors and dL_dshs_rest");
-            kern = gp_preprocess_bwd_split_kernel;
+            kern = af.on ? gp_preprocess_bwd_split_adam_kernel : gp_preprocess_bwd_split_kernel;
         } else if (in->shs && d.M == 16 && al16) {
             kern = gp_preprocess_bwd_sh16_kernel;
         }
         if (g->accumulate_shs && kern == gp_preprocess_bwd_kernel)
             GP_FAIL("accumulate_shs needs the staged SH kernels (16 coeffs, 16-byte aligned)");      // (before anything is written)
-        hipLaunchKernelGGL(kern, dim3(gp_blocks(N, 256)), dim3(256), 0, s, d, in->means3D, in->scales, in->rotations, in->shs,
+        const bool sha = kern == gp_preprocess_bwd_split_adam_kernel;      // (its own workgroup shape)
+        hipLaunchKernelGGL(kern, dim3(gp_blocks(N, sha ? GP_PB_ADAM_GAUSSIANS : 256)), dim3(sha ? GP_PB_ADAM_THREADS : 256), 0, s, d,
+                           in->means3D, in->scales, in->rotations, in->shs,
                            in->shs_rest, in->cov3D_precomp, st->viewmatrix, st->projmatrix, st->campos, fwd->radii, gl.clamped,
                            g_mean2D, g_conic, g_opacity, g_color, g_depth, g->dL_dmeans3D, g->dL_dmeans2D, g->dL_dshs,
                            g->dL_dshs_rest, in->shs ? nullptr : g->dL_dcolors_precomp, g->dL_dopacities, g->dL_dscales,

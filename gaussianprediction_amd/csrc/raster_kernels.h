@@ -86,6 +86,8 @@ __global__ __launch_bounds__(1024) void gp_bwd_prologue_kernel(const int2* __res
 __global__ __launch_bounds__(256) void gp_preprocess_bwd_kernel(GP_PB_ARGS);
 __global__ __launch_bounds__(256) void gp_preprocess_bwd_sh16_kernel(GP_PB_ARGS);
 __global__ __launch_bounds__(256) void gp_preprocess_bwd_split_kernel(GP_PB_ARGS);
+constexpr int GP_PB_ADAM_GAUSSIANS = 64, GP_PB_ADAM_THREADS = 128;      // per workgroup (63 floats of LDS per Gaussian)
+__global__ __launch_bounds__(GP_PB_ADAM_THREADS) void gp_preprocess_bwd_split_adam_kernel(GP_PB_ARGS);      // af.on: the SH Adam step inside it
 
 #define GP_CF_ARGS RasterDims d, const int2* __restrict__ ranges, const uint32_t* __restrict__ point_list, const float4* __restrict__ rec, \
     const float* __restrict__ bg, float* __restrict__ out_color, float* __restrict__ out_depth, int32_t* __restrict__ out_tidx, \

@@ -165,27 +165,27 @@ __device__ __forceinline__ void sh_to_rgb(int deg, const float* __restrict__ sh,
 // thread picks its own coefficients at an odd LDS stride (conflict-free).
 // SH_MODE 0: generic (direct global loads)  1: one tensor, M = 16  2: dc + rest, M = 16
 // ------------------------------------------------------------------------------------------------
-template <int CNT>
+template <int CNT, int STRIDE = (CNT | 1), int NT = 256>      // (NT threads: NT * 4 floats per trip)
 __device__ __forceinline__ void stage_sh(float* s_sh, const float* __restrict__ src, int nblk, int tid) {
-    constexpr int STRIDE = CNT | 1;
+    constexpr int CH = NT * 4;
     const int total = nblk * CNT;
     int e = tid * 4;
-    for (; e + 3 * 1024 + 3 < total; e += 4 * 1024) {      // four 16-byte loads in flight per thread (see adam_unstage_sh)
+    for (; e + 3 * CH + 3 < total; e += 4 * CH) {      // four 16-byte loads in flight per thread (see adam_unstage_sh)
         float4 f[4];
 #pragma unroll
-        for (int w = 0; w < 4; ++w) f[w] = *(const float4*)(src + e + w * 1024);
+        for (int w = 0; w < 4; ++w) f[w] = *(const float4*)(src + e + w * CH);
 #pragma unroll
         for (int w = 0; w < 4; ++w) {
             const float* fv = (const float*)&f[w];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                const int idx = e + w * 1024 + u;
+                const int idx = e + w * CH + u;
                 const int g = idx / CNT, k = idx - g * CNT;
                 s_sh[g * STRIDE + k] = fv[u];
             }
         }
     }
-    for (; e < total; e += 1024) {
+    for (; e < total; e += CH) {
         float v[4];
         if (e + 3 < total) {
             const float4 f = *(const float4*)(src + e);
@@ -1568,73 +1568,81 @@ __global__ __launch_bounds__(64) void gp_composite_bwd_depth_kernel(GP_CB_ARGS) 
     gp_composite_bwd_body<true, GP_BWD_ROWS, GP_BWD_COLS>(d, ranges, point_list, smask, rec, bg, out_color, out_depth, final_T, n_contrib, dL_dpix, dL_dpixdepth, g_mean2D, g_conic, g_opacity, g_color, g_depth, order);
 }
 
-// Adam on the workgroup's span of SH-rest coefficients, gradients taken from LDS (instead of unstage_sh + a later pass of the
-// optimizer kernel over the same 180 B per Gaussian: the gradient is neither written nor read back, the coefficients are still in L2)
-template <int CNT>
-__device__ __forceinline__ void adam_unstage_sh(const float* s_sh, const AdamFuseDev& af, size_t off, int nblk, int tid) {
-    constexpr int STRIDE = CNT | 1;
-    const int total = nblk * CNT;
+// The projection backward with the SH coefficients' Adam step inside it (SH_MODE 2, gp_adam_fuse) keeps a row of SHA_ROW floats per
+// Gaussian in LDS: the 45 staged coefficients, left as they were read (they are the update's `p`: features_rest crosses HBM once), the
+// 15 basis values Y_k of the view direction and the 3 effective colour gradients.  Every gradient is the product Y_k g_ch of two of
+// them, formed by the update's stream exactly as the gradient-writing path forms it: one multiplication, the same two operands.
+constexpr int SHA_Y = 45, SHA_G = 60, SHA_ROW = 63;     // (odd row stride: a thread per row is conflict-free)
+
+// Adam on the workgroup's span of SH-rest coefficients (instead of unstage_sh + a later pass of the optimizer kernel over the same
+// 180 B per Gaussian: the gradient is neither written nor read back).  Only the two moments are fetched: 20 B per coefficient, read
+// and write.  `lim` = 3 (D + 1)^2 - 3: the coefficients above the active degree take the gradient +0, as dL_dshs_rest states it.
+template <int NT>
+__device__ __forceinline__ void adam_unstage_sh(const float* s_sh, const AdamFuseDev& af, size_t off, int nblk, int tid, int lim) {
+    constexpr int CH = NT * 4;
+    const int total = nblk * 45;
     float* __restrict__ p = af.p_rest + off; float* __restrict__ m = af.m_rest + off; float* __restrict__ v = af.v_rest + off;
-    // The stream that bounds the kernel (28 B per coefficient, 1.35 GB per launch at 1 M Gaussians).  One 1024-float chunk per
-    // iteration put three 16-byte loads in flight per thread, twelve waves per CU: ~36 KB per CU, i.e. latency x bandwidth for
-    // ~5 TB/s and no more.  AU chunks per iteration: 3 AU loads in flight before the first update.
-    constexpr int AU = 3;
-    int e = tid * 4;
-    for (; e + (AU - 1) * 1024 + 3 < total; e += AU * 1024) {
-        float4 pv[AU], mv[AU], vv[AU];
+    auto update = [&](int idx, float& pp, float& mm, float& vq) {
+        const int gi = idx / 45, k = idx - gi * 45;
+        const float* row = s_sh + gi * SHA_ROW;
+        const float g = k < lim ? row[SHA_Y + k / 3] * row[SHA_G + k % 3] : 0.f;
+        pp = row[k];
+        gp_adam_update(pp, g, mm, vq, af.b1, af.b2, af.eps, af.step_rest, af.bc2_sqrt);
+    };
+    // The stream that bounds the kernel: two 16-byte loads per thread and chunk of NT vectors, AU chunks fetched together (a full
+    // workgroup's 5.6 chunks: one round trip).  Every load is issued (at a clamped address past the span's end) before the first
+    // update; a chunk's last vector may be ragged in a partial workgroup (45 nblk is odd).  The kernel is not bound by bytes alone
+    // (the update holds an IEEE square root and two divisions per coefficient, a long dependent chain): what it needs is
+    // waves, profiles/preprocess_bwd_sh_once_ab.txt -- 256 Gaussians and threads per workgroup (two workgroups per CU by LDS) lost
+    // 5 - 7 % to the in-place form, 64 Gaussians under 128 threads (sixteen waves per CU, by registers) gains 5 %; AU = 3 and 12: slower.
+    constexpr int AU = 6;
+    for (int e = tid * 4; e < total; e += AU * CH) {
+        float4 mv[AU], vv[AU];
 #pragma unroll
         for (int c = 0; c < AU; ++c) {
-            pv[c] = *(const float4*)(p + e + 1024 * c); mv[c] = *(const float4*)(m + e + 1024 * c); vv[c] = *(const float4*)(v + e + 1024 * c);
+            const int ec = e + CH * c, el = ec + 3 < total ? ec : 0;
+            mv[c] = *(const float4*)(m + el); vv[c] = *(const float4*)(v + el);
         }
 #pragma unroll
         for (int c = 0; c < AU; ++c) {
-            float* pp = (float*)&pv[c]; float* mm = (float*)&mv[c]; float* vq = (float*)&vv[c];
+            const int ec = e + CH * c;
+            if (ec + 3 < total) {
+                float4 pv;
+                float* pp = (float*)&pv; float* mm = (float*)&mv[c]; float* vq = (float*)&vv[c];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int idx = e + 1024 * c + u;
-                const int gi = idx / CNT, k = idx - gi * CNT;
-                gp_adam_update(pp[u], s_sh[gi * STRIDE + k], mm[u], vq[u], af.b1, af.b2, af.eps, af.step_rest, af.bc2_sqrt);
+                for (int u = 0; u < 4; ++u) update(ec + u, pp[u], mm[u], vq[u]);
+                *(float4*)(p + ec) = pv; *(float4*)(m + ec) = mv[c]; *(float4*)(v + ec) = vv[c];
+            } else {
+                for (int idx = ec; idx < total; ++idx) update(idx, p[idx], m[idx], v[idx]);
             }
-        }
-#pragma unroll
-        for (int c = 0; c < AU; ++c) {
-            *(float4*)(p + e + 1024 * c) = pv[c]; *(float4*)(m + e + 1024 * c) = mv[c]; *(float4*)(v + e + 1024 * c) = vv[c];
         }
     }
-    {   // the rest -- at most AU - 1 whole chunks and one ragged 16 bytes -- fetched together as well (one chunk per iteration,
-        // these were two more dependent round trips per thread: as many as the whole unrolled part above)
-        float4 pv[AU - 1], mv[AU - 1], vv[AU - 1];
-        bool ok[AU - 1];
+}
+
+// Real SH basis of degrees 1..3 at the unit direction (x, y, z): Y[k], k = 1..15, zero above degree D.  The gradient of coefficient
+// k in channel ch is Y[k] g_ch.
+__device__ __forceinline__ void sh_basis(int D, float x, float y, float z, float* Y) {
 #pragma unroll
-        for (int c = 0; c < AU - 1; ++c) {
-            const int ec = e + 1024 * c;
-            ok[c] = ec + 3 < total;
-            const int el = ok[c] ? ec : 0;
-            pv[c] = *(const float4*)(p + el); mv[c] = *(const float4*)(m + el); vv[c] = *(const float4*)(v + el);
-        }
-#pragma unroll
-        for (int c = 0; c < AU - 1; ++c) {
-            if (!ok[c]) continue;
-            float* pp = (float*)&pv[c]; float* mm = (float*)&mv[c]; float* vq = (float*)&vv[c];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int idx = e + 1024 * c + u;
-                const int gi = idx / CNT, k = idx - gi * CNT;
-                gp_adam_update(pp[u], s_sh[gi * STRIDE + k], mm[u], vq[u], af.b1, af.b2, af.eps, af.step_rest, af.bc2_sqrt);
-            }
-            *(float4*)(p + e + 1024 * c) = pv[c]; *(float4*)(m + e + 1024 * c) = mv[c]; *(float4*)(v + e + 1024 * c) = vv[c];
-        }
-#pragma unroll
-        for (int c = 0; c < AU - 1; ++c) {              // a ragged last vector (partial workgroups only)
-            const int ec = e + 1024 * c;
-            if (!ok[c] && ec < total) {
-                for (int u = 0; u < 4; ++u) {
-                    const int idx = ec + u;
-                    if (idx < total) {
-                        const int gi = idx / CNT, k = idx - gi * CNT;
-                        gp_adam_update(p[idx], s_sh[gi * STRIDE + k], m[idx], v[idx], af.b1, af.b2, af.eps, af.step_rest, af.bc2_sqrt);
-                    }
-                }
+    for (int k = 0; k < 16; ++k) Y[k] = 0.f;
+    if (D > 0) {
+        Y[1] = -SH_C1 * y;
+        Y[2] = SH_C1 * z;
+        Y[3] = -SH_C1 * x;
+        if (D > 1) {
+            const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
+            Y[4] = SH_C2[0] * xy;
+            Y[5] = SH_C2[1] * yz;
+            Y[6] = SH_C2[2] * (2.f * zz - xx - yy);
+            Y[7] = SH_C2[3] * xz;
+            Y[8] = SH_C2[4] * (xx - yy);
+            if (D > 2) {
+                Y[9] = SH_C3[0] * y * (3.f * xx - yy);
+                Y[10] = SH_C3[1] * xy * z;
+                Y[11] = SH_C3[2] * y * (4.f * zz - xx - yy);
+                Y[12] = SH_C3[3] * z * (2.f * zz - 3.f * xx - 3.f * yy);
+                Y[13] = SH_C3[4] * x * (4.f * zz - xx - yy);
+                Y[14] = SH_C3[5] * z * (xx - yy);
+                Y[15] = SH_C3[6] * x * (xx - 3.f * yy);
             }
         }
     }
@@ -1643,7 +1651,8 @@ __device__ __forceinline__ void adam_unstage_sh(const float* s_sh, const AdamFus
 // ------------------------------------------------------------------------------------------------
 // preprocess backward (per Gaussian) -- mirrors gpo_preprocess_bwd of the oracle
 // ------------------------------------------------------------------------------------------------
-template <int SH_MODE>
+// SH_ADAM (SH_MODE 2 with gp_adam_fuse on, a kernel of its own): the LDS rows of adam_unstage_sh instead of the in-place gradients.
+template <int SH_MODE, bool SH_ADAM = false>
 __device__ __forceinline__ void preprocess_bwd_body(
     RasterDims d, const float* __restrict__ means3D, const float* __restrict__ scales, const float* __restrict__ rotations,
     const float* __restrict__ shs, const float* __restrict__ shs_rest, const float* __restrict__ cov3D_precomp,
@@ -1654,15 +1663,19 @@ __device__ __forceinline__ void preprocess_bwd_body(
     float* __restrict__ dL_dshs, float* __restrict__ dL_dshs_rest, float* __restrict__ dL_dcolors,
     float* __restrict__ dL_dopacities, float* __restrict__ dL_dscales, float* __restrict__ dL_drots,
     float* __restrict__ dL_dcov3D, int accumulate_shs, AdamFuseDev af) {
-    __shared__ float s_sh[SH_MODE == 0 ? 1 : 256 * 49];
+    static_assert(!SH_ADAM || SH_MODE == 2, "the fused SH Adam step is the split layout's");
+    // SH_ADAM: NG Gaussians per workgroup of NT >= NG threads.  The first NG threads own a Gaussian each; ALL of them stage the span
+    // and run the update's stream (the LDS a Gaussian needs bounds the Gaussians per CU, not the waves that stream for them).
+    constexpr int NT = SH_ADAM ? GP_PB_ADAM_THREADS : 256, NG = SH_ADAM ? GP_PB_ADAM_GAUSSIANS : 256;
+    __shared__ float s_sh[SH_MODE == 0 ? 1 : NG * (SH_ADAM ? SHA_ROW : 49)];
     const int tid = threadIdx.x;
-    const int base = blockIdx.x * 256;
-    const int i = base + tid;
-    const int nblk = min(256, d.N - base);
+    const int base = blockIdx.x * NG;
+    const int i = tid < NG ? base + tid : d.N;                  // (d.N: no Gaussian of its own)
+    const int nblk = min(NG, d.N - base);
     const bool use_sh = dL_dcolors == nullptr;
     // SH_MODE 1/2: coefficients are staged in LDS and their gradients REPLACE them in place (one channel's 16
-    // coefficients are in registers at a time), then leave as one coalesced span per workgroup.
-    constexpr int SROW = SH_MODE == 1 ? 49 : 45;        // LDS row stride (odd: conflict-free)
+    // coefficients are in registers at a time), then leave as one coalesced span per workgroup.  (SH_ADAM: see SHA_ROW.)
+    constexpr int SROW = SH_ADAM ? SHA_ROW : SH_MODE == 1 ? 49 : 45;        // LDS row stride (odd: conflict-free)
     constexpr int SOFF = SH_MODE == 1 ? 0 : 3;          // first coefficient float held in the row
     float dsh_dc[3] = {0.f, 0.f, 0.f};                  // SH_MODE 2: gradient of the dc coefficient (separate tensor)
     // Everything the thread reads from global memory, issued TOGETHER up front, in front of the SH staging (they ride on its first round trip) (clamped index, unconditional): as loads placed
@@ -1686,7 +1699,9 @@ __device__ __forceinline__ void preprocess_bwd_body(
     const float acc_mean2D[2] = {A0.x, A0.y}, acc_conic[3] = {A0.z, A0.w, A1.x}, acc_opacity = A1.y,
                 acc_color[3] = {A1.z, A1.w, A2.x}, acc_depth = A2.y;
     if (SH_MODE != 0) {
-        if (use_sh && d.D > 0) {
+        if (SH_ADAM) {      // (at degree 0 as well: the staged coefficients are the update's `p`)
+            stage_sh<45, SHA_ROW, NT>(s_sh, shs_rest + (size_t)base * 45, nblk, tid);
+        } else if (use_sh && d.D > 0) {
             if (SH_MODE == 1) stage_sh<48>(s_sh, shs + (size_t)base * 48, nblk, tid);
             if (SH_MODE == 2) stage_sh<45>(s_sh, shs_rest + (size_t)base * 45, nblk, tid);
         }
@@ -1795,6 +1810,8 @@ __device__ __forceinline__ void preprocess_bwd_body(
         const float* sh_g = shs + (size_t)i * d.M * 3;          // SH_MODE 0
         float* dsh_g = dL_dshs + (size_t)i * d.M * 3;           // SH_MODE 0
         float* row = s_sh + tid * SROW - SOFF;                  // SH_MODE 1/2: row[3 k + ch], k >= SOFF / 3
+        float Y[16];
+        sh_basis(D, x, y, z, Y);
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) {
             const float g = ((cl >> ch) & 1) ? 0.f : acc_color[ch];
@@ -1803,36 +1820,21 @@ __device__ __forceinline__ void preprocess_bwd_body(
 #pragma unroll
             for (int k = 1; k < 16; ++k) sh[k] = (k < used) ? (SH_MODE == 0 ? sh_g[3 * k + ch] : row[3 * k + ch]) : 0.f;
             float dsh[16];
-#pragma unroll
-            for (int k = 0; k < 16; ++k) dsh[k] = 0.f;
             dsh[0] = SH_C0 * g;
+#pragma unroll
+            for (int k = 1; k < 16; ++k) dsh[k] = (k < used) ? Y[k] * g : 0.f;
             if (D > 0) {
-                dsh[1] = -SH_C1 * y * g;
-                dsh[2] = SH_C1 * z * g;
-                dsh[3] = -SH_C1 * x * g;
                 float ddx = -SH_C1 * sh[3];
                 float ddy = -SH_C1 * sh[1];
                 float ddz = SH_C1 * sh[2];
                 if (D > 1) {
                     const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-                    dsh[4] = SH_C2[0] * xy * g;
-                    dsh[5] = SH_C2[1] * yz * g;
-                    dsh[6] = SH_C2[2] * (2.f * zz - xx - yy) * g;
-                    dsh[7] = SH_C2[3] * xz * g;
-                    dsh[8] = SH_C2[4] * (xx - yy) * g;
                     ddx += SH_C2[0] * y * sh[4] + SH_C2[2] * 2.f * -x * sh[6] + SH_C2[3] * z * sh[7] +
                            SH_C2[4] * 2.f * x * sh[8];
                     ddy += SH_C2[0] * x * sh[4] + SH_C2[1] * z * sh[5] + SH_C2[2] * 2.f * -y * sh[6] +
                            SH_C2[4] * 2.f * -y * sh[8];
                     ddz += SH_C2[1] * y * sh[5] + SH_C2[2] * 4.f * z * sh[6] + SH_C2[3] * x * sh[7];
                     if (D > 2) {
-                        dsh[9] = SH_C3[0] * y * (3.f * xx - yy) * g;
-                        dsh[10] = SH_C3[1] * xy * z * g;
-                        dsh[11] = SH_C3[2] * y * (4.f * zz - xx - yy) * g;
-                        dsh[12] = SH_C3[3] * z * (2.f * zz - 3.f * xx - 3.f * yy) * g;
-                        dsh[13] = SH_C3[4] * x * (4.f * zz - xx - yy) * g;
-                        dsh[14] = SH_C3[5] * z * (xx - yy) * g;
-                        dsh[15] = SH_C3[6] * x * (xx - 3.f * yy) * g;
                         ddx += SH_C3[0] * sh[9] * 6.f * xy + SH_C3[1] * sh[10] * yz +
                                SH_C3[2] * sh[11] * -2.f * xy + SH_C3[3] * sh[12] * -6.f * xz +
                                SH_C3[4] * sh[13] * (4.f * zz - 3.f * xx - yy) + SH_C3[5] * sh[14] * 2.f * xz +
@@ -1852,11 +1854,18 @@ __device__ __forceinline__ void preprocess_bwd_body(
 #pragma unroll
                 for (int k = 0; k < 16; ++k) if (k < d.M) dsh_g[3 * k + ch] = vis ? dsh[k] : 0.f;
                 for (int k = 16; k < d.M; ++k) dsh_g[3 * k + ch] = 0.f;
+            } else if (SH_ADAM) {       // the coefficients stay; the stream multiplies the two factors (NaN 0 of a culled Gaussian at
+                dsh_dc[ch] = vis ? dsh[0] : 0.f;                            // the camera centre must not reach the moments: both selected)
+                row[SOFF + SHA_G + ch] = vis ? g : 0.f;
             } else {
                 if (SH_MODE == 2) dsh_dc[ch] = vis ? dsh[0] : 0.f; else row[ch] = vis ? dsh[0] : 0.f;
 #pragma unroll
                 for (int k = 1; k < 16; ++k) row[3 * k + ch] = vis ? dsh[k] : 0.f;
             }
+        }
+        if (SH_ADAM) {
+#pragma unroll
+            for (int k = 1; k < 16; ++k) row[SOFF + SHA_Y + k - 1] = vis ? Y[k] : 0.f;
         }
         const float dot = x * ddir0 + y * ddir1 + z * ddir2;
         gm0 += (ddir0 - x * dot) * inv;
@@ -1903,7 +1912,7 @@ __device__ __forceinline__ void preprocess_bwd_body(
         __syncthreads();
         if (SH_MODE == 1) {
             unstage_sh<48>(s_sh, dL_dshs + (size_t)base * 48, nblk, tid, accumulate_shs != 0);
-        } else if (af.on) {
+        } else if (SH_ADAM) {
             // the optimizer step of the SH coefficients, here: no gradient leaves the kernel (skip: an invalid frame, nothing is touched)
             if (!(af.skip && *af.skip != 0)) {
                 if (i < d.N) {      // (all nine values first: through the references the three updates were nine dependent round trips)
@@ -1915,7 +1924,7 @@ __device__ __forceinline__ void preprocess_bwd_body(
 #pragma unroll
                     for (int k = 0; k < 3; ++k) { af.p_dc[3 * (size_t)i + k] = pp[k]; af.m_dc[3 * (size_t)i + k] = mm[k]; af.v_dc[3 * (size_t)i + k] = vq[k]; }
                 }
-                adam_unstage_sh<45>(s_sh, af, (size_t)base * 45, nblk, tid);
+                adam_unstage_sh<NT>(s_sh, af, (size_t)base * 45, nblk, tid, 3 * (d.D + 1) * (d.D + 1) - 3);
             }
         } else {
             if (i < d.N) {
@@ -1933,3 +1942,4 @@ __device__ __forceinline__ void preprocess_bwd_body(
 __global__ __launch_bounds__(256) void gp_preprocess_bwd_kernel(GP_PB_ARGS) { preprocess_bwd_body<0>(PB_PASS); }
 __global__ __launch_bounds__(256) void gp_preprocess_bwd_sh16_kernel(GP_PB_ARGS) { preprocess_bwd_body<1>(PB_PASS); }
 __global__ __launch_bounds__(256) void gp_preprocess_bwd_split_kernel(GP_PB_ARGS) { preprocess_bwd_body<2>(PB_PASS); }
+__global__ __launch_bounds__(GP_PB_ADAM_THREADS) void gp_preprocess_bwd_split_adam_kernel(GP_PB_ARGS) { preprocess_bwd_body<2, true>(PB_PASS); }

@@ -127,9 +127,10 @@ typedef struct gp_raster_saved {
 } gp_raster_saved;
 
 /* Optional: torch.optim.Adam's step of the SH coefficients applied INSIDE gp_raster_backward (extension; the reference runs
- * optimizer.step() afterwards, train.py:196).  The preprocess backward holds a workgroup's SH gradients in LDS and the
- * coefficients are still in L2: updating them there saves writing the gradient (192 B per Gaussian) and reading gradient +
- * coefficients back in the optimizer kernel.  Same arithmetic as gp_adam_step_multi, bit for bit (one shared device function).
+ * optimizer.step() afterwards, train.py:196).  The preprocess backward holds a workgroup's SH coefficients in LDS (staged for the
+ * view-direction gradient) beside the two factors of their gradients: updating them there saves writing the gradient (192 B per
+ * Gaussian) and reading gradient + coefficients back in the optimizer kernel -- the coefficients cross HBM once per backward, only the
+ * moments are fetched for the update.  Same arithmetic as gp_adam_step_multi, bit for bit (one shared device function).
  * in->shs / in->shs_rest are then UPDATED IN PLACE (they must be the parameters themselves), dL_dshs / dL_dshs_rest are not
  * written and may be NULL.  skip_flag: optional device word, non-zero = leave parameters and moments untouched. */
 typedef struct gp_adam_fuse {
