@@ -18,20 +18,17 @@ from __future__ import annotations
 import ctypes as C
 import os
 import struct
-from concurrent.futures import ThreadPoolExecutor
 from types import SimpleNamespace
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, decode_stage
+from .decode_stage import DST_F32, DST_U8, MAX_BATCH, READER_THREADS  # noqa: F401  (what include/gp_jpeg_decode.h calls GP_JPEG_DECODE_*)
 
 GP_JPEG_DECODE_ABI_VERSION = 1      # include/gp_jpeg_decode.h
-MAX_BATCH = 65535
 TABLE_BYTES = 1232
-DST_U8, DST_F32 = 0, 1
 SUB_420, SUB_444 = 0, 1             # GP_JPEG_420, GP_JPEG_444 of include/gp_jpeg.h
-READER_THREADS = 4
 AVI_BATCH = 32                      # frames per decode call of decode_avi
 
 STATUS = {0: "OK", 1: "TRUNCATED", 2: "NO_CODE", 3: "CATEGORY", 4: "RUN", 5: "TRAILING", 6: "MARKER", 7: "HUFFMAN_TABLE", 8: "TABLE",
@@ -231,26 +228,9 @@ def pieces(item):
     return [bytes(item.scan[a:a + n]) for a, n in zip(item.seg_at.tolist(), item.seg_len.tolist())]
 
 
-def _device(device):
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError(f"jpeg_decode: device {device} -- HIP kernels only (no CPU fallback)")
-    return torch.device("cuda", torch.cuda.current_device()) if device.index is None else device
-
-
-def _arguments(device, dtype):
-    device = _device(device)
-    if dtype not in (torch.uint8, torch.float32):
-        raise RuntimeError(f"jpeg_decode: dtype must be torch.uint8 or torch.float32 (got {dtype})")
-    return device
-
-
 def groups(items):
     """The images by shape and subsampling, in order of first appearance: [((H, W, sub), [index])]."""
-    by_shape = {}
-    for i, it in enumerate(items):
-        by_shape.setdefault((it.H, it.W, it.sub), []).append(i)
-    return [(key, idx[lo:lo + MAX_BATCH]) for key, idx in by_shape.items() for lo in range(0, len(idx), MAX_BATCH)]
+    return decode_stage.groups(items, lambda it: (it.H, it.W, it.sub))
 
 
 def tables(items, idx):
@@ -270,63 +250,30 @@ def tables(items, idx):
     return np.concatenate(seg), image_seg, copies, at, most
 
 
+def plans(items, shapes):
+    """decode_stage's plan of every shape group: its `tables` and the images' quantisation and Huffman tables."""
+    return [decode_stage.plan(idx, (3, H, W), *tables(items, idx), tables=b"".join(items[i].tables for i in idx)) for (H, W, _), idx in shapes]
+
+
 def stage(items, shapes, pool=None):
-    """The pinned staging buffer of one pass: all segment tables (int64), all image tables (int32), every image's quantisation and
-    Huffman tables, then every group's scans.  Returns a namespace: buffer, plans (per group: seg,
-    image_seg, bytes, most and where its parts lie)."""
-    plans, nseg_all, nimg_all, ntab_all, pay_all = [], 0, 0, 0, 0
-    for _, idx in shapes:
-        seg, image_seg, copies, at, most = tables(items, idx)
-        plans.append(SimpleNamespace(seg=seg, image_seg=image_seg, bytes=at, copies=copies, most=most, seg_at=nseg_all * 40, tab_at=ntab_all * TABLE_BYTES,
-                                     pay_at=pay_all, tables=b"".join(items[i].tables for i in idx)))
-        nseg_all += len(seg)
-        nimg_all += len(image_seg)
-        ntab_all += len(idx)
-        pay_all += -(-at // 16) * 16
-    img_off = nseg_all * 40
-    tab_off = -(-(img_off + 4 * nimg_all) // 16) * 16
-    pay_off = -(-(tab_off + ntab_all * TABLE_BYTES) // 256) * 256
-    for pl in plans:
-        pl.img_at, img_off = img_off, img_off + 4 * len(pl.image_seg)
-        pl.tab_at += tab_off
-        pl.pay_at += pay_off
-    staging = torch.empty(pay_off + pay_all + 16, dtype=torch.uint8, pin_memory=True)
-    host = staging.numpy()
-    host[:nseg_all * 40].view(np.int64)[:] = np.concatenate([pl.seg for pl in plans]).reshape(-1)
-    host[nseg_all * 40:img_off].view(np.int32)[:] = np.array([v for pl in plans for v in pl.image_seg], dtype=np.int32)
-    for pl in plans:
-        host[pl.tab_at:pl.tab_at + len(pl.tables)] = np.frombuffer(pl.tables, dtype=np.uint8)
-
-    def copy(job):
-        at, piece = job
-        host[at:at + len(piece)] = np.frombuffer(piece, dtype=np.uint8)
-
-    jobs = [(pl.pay_at + at, piece) for pl in plans for at, piece in pl.copies]
-    if pool is not None and len(jobs) > 1:
-        list(pool.map(copy, jobs, chunksize=max(1, len(jobs) // (4 * READER_THREADS))))
-    else:
-        for job in jobs:
-            copy(job)
-    return SimpleNamespace(buffer=staging, plans=plans)
+    """The pinned staging buffer of one pass (decode_stage.stage): the segment and image tables, every image's quantisation and Huffman
+    tables, then every group's scans.  Returns a namespace: buffer, plans (per group: seg, image_seg, bytes, most and where its parts lie)."""
+    return decode_stage.stage(plans(items, shapes), pool)
 
 
 def launch(staged, up, shapes, words, *, device, dtype, guard=0):
     """One gp_jpeg_decode call per shape group on `up`, the staging buffer's copy on the device; words: int32 [images] on the device
     for the status words, in group order.  Nothing is read.  Returns (per group the [B, 3 H W + guard] output buffer)."""
-    l, slots, done = lib(), [], 0
-    with _lib.on_device(device):
-        for ((H, W, sub), idx), pl in zip(shapes, staged.plans):
-            B, stride = len(idx), 3 * H * W + int(guard)
-            scratch = _lib.scratch(l.gp_jpeg_decode_scratch_bytes, B, H, W, sub, len(pl.seg), device=device)
-            dst = torch.empty(B, stride, dtype=dtype, device=device)
-            if guard:
-                dst.view(torch.uint8).fill_(0xA5)
-            _lib.check(l.gp_jpeg_decode(B, H, W, sub, DST_U8 if dtype == torch.uint8 else DST_F32, up[pl.pay_at:], pl.bytes, up[pl.seg_at:],
-                                        len(pl.seg), up[pl.img_at:], pl.most, up[pl.tab_at:], dst, stride, words[done:], scratch,
-                                        _lib.stream_ptr(device)), "gp_jpeg_decode")
-            slots.append(dst)
-            done += B
-    return slots
+    l = lib()
+
+    def call(group, pl, dst, stride, done):
+        (H, W, sub), idx = group
+        scratch = _lib.scratch(l.gp_jpeg_decode_scratch_bytes, len(idx), H, W, sub, len(pl.seg), device=device)
+        _lib.check(l.gp_jpeg_decode(len(idx), H, W, sub, DST_U8 if dtype == torch.uint8 else DST_F32, up[pl.pay_at:], pl.bytes, up[pl.seg_at:],
+                                    len(pl.seg), up[pl.img_at:], pl.most, up[pl.tab_at:], dst, stride, words[done:], scratch,
+                                    _lib.stream_ptr(device)), "gp_jpeg_decode")
+
+    return decode_stage.launch(shapes, staged.plans, call, device=device, dtype=dtype, guard=guard)
 
 
 def decode_once(items, *, device, dtype=torch.uint8, guard=0, pool=None):
@@ -334,23 +281,15 @@ def decode_once(items, *, device, dtype=torch.uint8, guard=0, pool=None):
     of the status words.  Returns (images: a list of [3, H, W] device tensors, views of their group's batch; status: a list of ints;
     slots: per group the whole [B, 3 H W + guard] buffer, whose `guard` trailing elements per image were filled with 0xA5 bytes
     before the call -- the tests look at them)."""
-    device = _arguments(device, dtype)
+    device = decode_stage.arguments("jpeg_decode", device, dtype)
     if not items:
         return [], [], []
     shapes = groups(items)
-    staged = stage(items, shapes, pool)
-    with _lib.on_device(device):
-        up = staged.buffer.to(device, non_blocking=True)                        # the one copy
-        words = torch.empty(len(items), dtype=torch.int32, device=device)
-        slots = launch(staged, up, shapes, words, device=device, dtype=dtype, guard=guard)
-        read = words.cpu().tolist()                                             # the one read (it also ends the staging buffer's use)
-    images, status, k = [None] * len(items), [0] * len(items), 0
-    for ((H, W, _), idx), dst in zip(shapes, slots):
-        for b, i in enumerate(idx):
-            images[i] = dst[b, :3 * H * W].view(3, H, W)
-            status[i] = read[k]
-            k += 1
-    return images, status, slots
+    images, where, read, slots = decode_stage.once(
+        plans(items, shapes), (len(items),), device=device, pool=pool,
+        launch=lambda staged, up, words: launch(staged, up, shapes, words, device=device, dtype=dtype, guard=guard))
+    read = read.tolist()
+    return images, [read[k] for k in where], slots
 
 
 def _sync_flag(sync):
@@ -369,18 +308,14 @@ def decode(files, *, device, dtype=torch.uint8, names=None, sync=False, resize=N
     pass, so the pixels and every error are those of sync=False.  Off by default.
     resize: (width, height), or a callable (w, h) -> (width, height) -- every image is decoded as uint8 and resized as Image.resize
     does it, byte for byte (resize_ops.resize, filter `resample`), one batched call per shape group; `dtype` applies to the result."""
-    _arguments(device, dtype)                                                   # (the device is checked before any file is looked at)
+    decode_stage.arguments("jpeg_decode", device, dtype)                        # (the device is checked before any file is looked at)
     sync = _sync_flag(sync)
     out_dtype = dtype
     if resize is not None:
         from . import resize_ops
         resize_ops.filter_id(resample)
         dtype = torch.uint8
-    files = list(files)
-    names = [f"<file {i}>" for i in range(len(files))] if names is None else [os.fspath(n) for n in names]
-    if len(names) != len(files):
-        raise RuntimeError(f"jpeg_decode: {len(files)} files but {len(names)} names")
-    items = [f if isinstance(f, SimpleNamespace) else parse(f, n) for f, n in zip(files, names)]
+    items = decode_stage.parsed("jpeg_decode", files, names, parse)
     if resize is not None:
         for it in items:
             resize_ops.target_size(resize, it.W, it.H, it.name)                 # (a target size of 0 names its file, before the device)
@@ -405,17 +340,9 @@ def decode(files, *, device, dtype=torch.uint8, names=None, sync=False, resize=N
 
 def decode_files(paths, *, device, dtype=torch.uint8, sync=False, resize=None, resample="bicubic"):
     """`decode` of files on disk: at most READER_THREADS threads read and parse them and fill the staging buffer."""
-    _arguments(device, dtype)
+    decode_stage.arguments("jpeg_decode", device, dtype)
     _sync_flag(sync)
-    paths = [os.fspath(p) for p in paths]
-
-    def load(path):
-        with open(path, "rb") as fp:
-            return parse(fp.read(), path)
-
-    with ThreadPoolExecutor(max_workers=max(1, min(READER_THREADS, len(paths)))) as pool:
-        items = list(pool.map(load, paths))
-        return decode(items, device=device, dtype=dtype, names=paths, sync=sync, resize=resize, resample=resample, _pool=pool)
+    return decode_stage.decode_files(paths, parse, decode, device=device, dtype=dtype, sync=sync, resize=resize, resample=resample)
 
 
 # ---- Motion-JPEG in AVI ----------------------------------------------------------------------------------------------------------------
@@ -480,7 +407,7 @@ def decode_avi(path, *, device, dtype=torch.uint8, frames=None, sync=False, resi
     `device`.  frames: the frame numbers to decode, in the order wanted (default: all).  AVI_BATCH frames per decode call.  sync: as
     `decode` -- the frames other encoders write carry no restart markers.  resize, resample: as `decode`; the result is then
     [F, 3, height, width]."""
-    device = _arguments(device, dtype)
+    device = decode_stage.arguments("jpeg_decode", device, dtype)
     _sync_flag(sync)
     if resize is not None:
         from . import resize_ops

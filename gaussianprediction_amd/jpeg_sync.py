@@ -12,7 +12,7 @@ import ctypes as ct
 
 import torch
 
-from . import _lib, jpeg_decode
+from . import _lib, decode_stage, jpeg_decode
 
 GP_JPEG_SYNC_ABI_VERSION = 1        # include/gp_jpeg_sync.h
 S = 128                             # GP_JPEG_SYNC_SUBSEQ_BYTES: bytes of the stuffed scan per lane
@@ -48,27 +48,24 @@ def launch(staged, up, shapes, words, *, device, dtype, guard=0):
     """One gp_jpeg_sync_decode call per shape group on `up`, the staging buffer's copy on the device; words: int32 [images, 5] on the
     device: per group its status words, then its info words.  Nothing is read.  Returns (per group the [B, 3 H W + guard] output
     buffer; per group (scratch, pad, bytes) where guard bytes were laid round the scratch)."""
-    l, slots, fences, done = lib(), [], [], 0
-    guard = int(guard)
-    pad = -(-guard // 256) * 256                                               # (the scratch itself stays 256-byte aligned)
-    with _lib.on_device(device):
-        for ((H, W, sub), idx), pl in zip(shapes, staged.plans):
-            B, stride = len(idx), 3 * H * W + guard
-            scratch = _lib.scratch(l.gp_jpeg_sync_scratch_bytes, B, H, W, sub, pl.bytes, device=device, extra=2 * pad)
-            n = scratch.numel() - 2 * pad
-            dst = torch.empty(B, stride, dtype=dtype, device=device)
-            if guard:
-                dst.view(torch.uint8).fill_(0xA5)
-                scratch[:pad].fill_(0xA5)
-                scratch[pad + n:].fill_(0xA5)
-                fences.append((scratch, pad, n))
-            group = words[done:done + B].view(-1)
-            _lib.check(l.gp_jpeg_sync_decode(B, H, W, sub, jpeg_decode.DST_U8 if dtype == torch.uint8 else jpeg_decode.DST_F32, up[pl.pay_at:], pl.bytes,
-                                             up[pl.seg_at:], len(pl.seg), up[pl.img_at:], pl.most, up[pl.tab_at:], dst, stride, group[:B], group[B:],
-                                             scratch[pad:], _lib.stream_ptr(device)), "gp_jpeg_sync_decode")
-            slots.append(dst)
-            done += B
-    return slots, fences
+    l, fences = lib(), []
+    pad = -(-int(guard) // 256) * 256                                          # (the scratch itself stays 256-byte aligned)
+
+    def call(group, pl, dst, stride, done):
+        (H, W, sub), idx = group
+        B = len(idx)
+        scratch = _lib.scratch(l.gp_jpeg_sync_scratch_bytes, B, H, W, sub, pl.bytes, device=device, extra=2 * pad)
+        n = scratch.numel() - 2 * pad
+        if guard:
+            scratch[:pad].fill_(0xA5)
+            scratch[pad + n:].fill_(0xA5)
+            fences.append((scratch, pad, n))
+        mine = words[done:done + B].view(-1)
+        _lib.check(l.gp_jpeg_sync_decode(B, H, W, sub, jpeg_decode.DST_U8 if dtype == torch.uint8 else jpeg_decode.DST_F32, up[pl.pay_at:], pl.bytes,
+                                         up[pl.seg_at:], len(pl.seg), up[pl.img_at:], pl.most, up[pl.tab_at:], dst, stride, mine[:B], mine[B:],
+                                         scratch[pad:], _lib.stream_ptr(device)), "gp_jpeg_sync_decode")
+
+    return decode_stage.launch(shapes, staged.plans, call, device=device, dtype=dtype, guard=guard), fences
 
 
 def decode_once(items, *, device, dtype=torch.uint8, guard=0, pool=None):
@@ -77,20 +74,21 @@ def decode_once(items, *, device, dtype=torch.uint8, guard=0, pool=None):
     of [3, H, W] device tensors; status: a list of OK / SERIAL; info: a list of (subsequences, chunks, most rounds inside a chunk,
     rounds across chunks)).  guard: that many elements behind every output slot, and that many bytes on both sides of the scratch
     buffer, are filled with 0xA5 before the call and checked after it (RuntimeError) -- the tests ask for it."""
-    device = jpeg_decode._arguments(device, dtype)
+    device = decode_stage.arguments("jpeg_sync", device, dtype)
     if not items:
         return [], [], []
     for it in items:
         if it.nseg != 1:
             raise RuntimeError(f"jpeg_sync: {it.name}: {it.nseg} restart intervals -- this stage takes files without restart markers (jpeg_decode.decode takes the rest)")
-    shapes = jpeg_decode.groups(items)
-    staged = jpeg_decode.stage(items, shapes, pool)
-    guard = int(guard)
+    shapes, guard, fences = jpeg_decode.groups(items), int(guard), []
+
+    def go(staged, up, words):
+        slots, fenced = launch(staged, up, shapes, words, device=device, dtype=dtype, guard=guard)
+        fences.extend(fenced)
+        return slots
+
+    images, _, read, slots = decode_stage.once(jpeg_decode.plans(items, shapes), (len(items), 5), go, device=device, pool=pool)
     with _lib.on_device(device):
-        up = staged.buffer.to(device, non_blocking=True)                        # the one copy
-        words = torch.empty(len(items), 5, dtype=torch.int32, device=device)
-        slots, fences = launch(staged, up, shapes, words, device=device, dtype=dtype, guard=guard)
-        read = words.cpu()                                                      # the one read (it also ends the staging buffer's use)
         for scratch, pad, n in fences:
             if not (bool((scratch[:pad] == 0xA5).all()) and bool((scratch[pad + n:] == 0xA5).all())):
                 raise RuntimeError("jpeg_sync: a kernel wrote outside its scratch buffer")
@@ -98,12 +96,11 @@ def decode_once(items, *, device, dtype=torch.uint8, guard=0, pool=None):
             for dst in slots:
                 if not bool((dst[:, -guard:].contiguous().view(torch.uint8) == 0xA5).all()):
                     raise RuntimeError("jpeg_sync: a kernel wrote behind an output slot")
-    images, status, info, k = [None] * len(items), [0] * len(items), [None] * len(items), 0
-    for ((H, W, _), idx), dst in zip(shapes, slots):
+    status, info, k = [0] * len(items), [None] * len(items), 0
+    for _, idx in shapes:
         B = len(idx)
         flat = read[k:k + B].reshape(-1).tolist()
         for b, i in enumerate(idx):
-            images[i] = dst[b, :3 * H * W].view(3, H, W)
             status[i] = flat[b]
             info[i] = tuple(v & 0xffffffff for v in flat[B + 4 * b:B + 4 * b + 4])
         k += B

@@ -14,23 +14,18 @@ back to.  HIP only: CPU devices raise."""
 from __future__ import annotations
 
 import ctypes as C
-import os
 import struct
 import zlib
-from concurrent.futures import ThreadPoolExecutor
 from types import SimpleNamespace
 
-import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, decode_stage
+from .decode_stage import DST_F32, DST_U8, MAX_BATCH, READER_THREADS  # noqa: F401  (what include/gp_png_decode.h calls GP_PNG_DECODE_*)
 
 GP_PNG_DECODE_ABI_VERSION = 1       # include/gp_png_decode.h
 BAND_BYTES = 16384                  # GP_PNG_BAND_BYTES of include/gp_png.h: where png_ops cuts its IDAT chunks
-MAX_BATCH = 65535
-DST_U8, DST_F32 = 0, 1
 MODE_SERIAL, MODE_BANDED = 1, 2
-READER_THREADS = 4
 SIGNATURE = b"\x89PNG\r\n\x1a\n"
 CHANNELS = {0: 1, 4: 2, 2: 3, 6: 4}  # colour type -> C
 
@@ -119,17 +114,8 @@ def parse(data, name="<bytes>"):
     return SimpleNamespace(name=name, H=H, W=W, C=Cn, S=S, pieces=pieces, banded=len(pieces) > 1 and len(pieces) == -(-S // BAND_BYTES))
 
 
-def _device(device):
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError(f"png_decode: device {device} -- HIP kernels only (no CPU fallback)")
-    return torch.device("cuda", torch.cuda.current_device()) if device.index is None else device
-
-
 def _arguments(device, dtype, background):
-    device = _device(device)
-    if dtype not in (torch.uint8, torch.float32):
-        raise RuntimeError(f"png_decode: dtype must be torch.uint8 or torch.float32 (got {dtype})")
+    device = decode_stage.arguments("png_decode", device, dtype)
     if background is not None:
         if not torch.is_tensor(background) or background.numel() != 3 or not background.dtype.is_floating_point:
             raise RuntimeError("png_decode: background must be a tensor of three floats")
@@ -141,18 +127,14 @@ def _arguments(device, dtype, background):
 
 def groups(items, channels=None, background=None):
     """The images by shape, in order of first appearance: [((H, W, C), C_out, [index])].  Checked before the device."""
-    by_shape = {}
-    for i, it in enumerate(items):
-        by_shape.setdefault((it.H, it.W, it.C), []).append(i)
     out = []
-    for (H, W, Cn), idx in by_shape.items():
+    for (H, W, Cn), idx in decode_stage.groups(items, lambda it: (it.H, it.W, it.C)):
         if background is not None and Cn != 4:
             raise ValueError(f"png_decode: {items[idx[0]].name}: a background composites RGBA images, this one has {Cn} channel(s)")
         c_out = 3 if background is not None and channels is None else Cn if channels is None else min(int(channels), Cn)
         if c_out < 1 or (background is not None and c_out != 3):
             raise ValueError(f"png_decode: {items[idx[0]].name}: channels = {c_out} of an image with {Cn}" + (" and a background" if background is not None else ""))
-        for lo in range(0, len(idx), MAX_BATCH):
-            out.append(((H, W, Cn), c_out, idx[lo:lo + MAX_BATCH]))
+        out.append(((H, W, Cn), c_out, idx))
     return out
 
 
@@ -175,56 +157,30 @@ def tables(items, banded, idx):
     return seg, image_seg, copies, at
 
 
+def plans(items, banded, shapes):
+    """decode_stage's plan of every shape group: its `tables`."""
+    return [decode_stage.plan(idx, (c_out, H, W), *tables(items, banded, idx)) for (H, W, _), c_out, idx in shapes]
+
+
 def stage(items, banded, shapes, pool=None):
-    """The pinned staging buffer of one pass: all segment tables (int64), all image tables (int32), then every group's joined IDAT
-    data with the chunk framing gone.  Returns a namespace: buffer, plans (per group: seg, image_seg, bytes and where its parts lie)."""
-    plans, nseg_all, nimg_all, pay_all = [], 0, 0, 0
-    for _, _, idx in shapes:
-        seg, image_seg, copies, at = tables(items, banded, idx)
-        plans.append(SimpleNamespace(seg=seg, image_seg=image_seg, bytes=at, copies=copies, seg_at=nseg_all * 40, pay_at=pay_all))
-        nseg_all += len(seg)
-        nimg_all += len(image_seg)
-        pay_all += -(-at // 16) * 16
-    img_off = nseg_all * 40
-    pay_off = -(-(img_off + 4 * nimg_all) // 256) * 256
-    for pl in plans:
-        pl.img_at, img_off = img_off, img_off + 4 * len(pl.image_seg)
-        pl.pay_at += pay_off
-    staging = torch.empty(pay_off + pay_all + 16, dtype=torch.uint8, pin_memory=True)
-    host = staging.numpy()
-    host[:nseg_all * 40].view(np.int64)[:] = np.array([s for pl in plans for s in pl.seg], dtype=np.int64).reshape(-1)
-    host[nseg_all * 40:img_off].view(np.int32)[:] = np.array([v for pl in plans for v in pl.image_seg], dtype=np.int32)
-
-    def copy(job):
-        at, piece = job
-        host[at:at + len(piece)] = np.frombuffer(piece, dtype=np.uint8)
-
-    jobs = [(pl.pay_at + at, piece) for pl in plans for at, piece in pl.copies]
-    if pool is not None and len(jobs) > 1:
-        list(pool.map(copy, jobs, chunksize=max(1, len(jobs) // (4 * READER_THREADS))))
-    else:
-        for job in jobs:
-            copy(job)
-    return SimpleNamespace(buffer=staging, plans=plans)
+    """The pinned staging buffer of one pass (decode_stage.stage): the segment and image tables, then every group's joined IDAT data with
+    the chunk framing gone.  Returns a namespace: buffer, plans (per group: seg, image_seg, bytes and where its parts lie)."""
+    return decode_stage.stage(plans(items, banded, shapes), pool)
 
 
 def launch(staged, up, shapes, words, *, device, dtype, background, guard=0):
     """One gp_png_decode call per shape group on `up`, the staging buffer's copy on the device; words: int32 [2, images] on the device
     for the status and mode words, in group order.  Nothing is read.  Returns (per group the [B, C_out H W + guard] output buffer)."""
-    l, slots, done = lib(), [], 0
-    with _lib.on_device(device):
-        for ((H, W, Cn), c_out, idx), pl in zip(shapes, staged.plans):
-            B, stride = len(idx), c_out * H * W + int(guard)
-            scratch = _lib.scratch(l.gp_png_decode_scratch_bytes, B, H, W, Cn, len(pl.seg), device=device)
-            dst = torch.empty(B, stride, dtype=dtype, device=device)
-            if guard:
-                dst.view(torch.uint8).fill_(0xA5)
-            _lib.check(l.gp_png_decode(B, H, W, Cn, c_out, DST_U8 if dtype == torch.uint8 else DST_F32, up[pl.pay_at:], pl.bytes,
-                                       up[pl.seg_at:], len(pl.seg), up[pl.img_at:], background, dst, stride, words[0, done:], words[1, done:],
-                                       scratch, _lib.stream_ptr(device)), "gp_png_decode")
-            slots.append(dst)
-            done += B
-    return slots
+    l = lib()
+
+    def call(group, pl, dst, stride, done):
+        (H, W, Cn), c_out, idx = group
+        scratch = _lib.scratch(l.gp_png_decode_scratch_bytes, len(idx), H, W, Cn, len(pl.seg), device=device)
+        _lib.check(l.gp_png_decode(len(idx), H, W, Cn, c_out, DST_U8 if dtype == torch.uint8 else DST_F32, up[pl.pay_at:], pl.bytes,
+                                   up[pl.seg_at:], len(pl.seg), up[pl.img_at:], background, dst, stride, words[0, done:], words[1, done:],
+                                   scratch, _lib.stream_ptr(device)), "gp_png_decode")
+
+    return decode_stage.launch(shapes, staged.plans, call, device=device, dtype=dtype, guard=guard)
 
 
 def decode_once(items, banded, *, device, dtype=torch.uint8, channels=None, background=None, guard=0, pool=None):
@@ -236,18 +192,10 @@ def decode_once(items, banded, *, device, dtype=torch.uint8, channels=None, back
     if not items:
         return [], [], [], []
     shapes = groups(items, channels, background)
-    staged = stage(items, banded, shapes, pool)
-    with _lib.on_device(device):
-        up = staged.buffer.to(device, non_blocking=True)                        # the one copy
-        words = torch.empty(2, len(items), dtype=torch.int32, device=device)
-        slots = launch(staged, up, shapes, words, device=device, dtype=dtype, background=background, guard=guard)
-        read = words.cpu().tolist()                                             # the one read (it also ends the staging buffer's use)
-    images, status, modes, k = [None] * len(items), [0] * len(items), [0] * len(items), 0
-    for ((H, W, Cn), c_out, idx), dst in zip(shapes, slots):
-        for b, i in enumerate(idx):
-            images[i] = dst[b, :c_out * H * W].view(c_out, H, W)
-            status[i], modes[i] = read[0][k], read[1][k]
-            k += 1
+    images, where, read, slots = decode_stage.once(
+        plans(items, banded, shapes), (2, len(items)), device=device, pool=pool,
+        launch=lambda staged, up, words: launch(staged, up, shapes, words, device=device, dtype=dtype, background=background, guard=guard))
+    status, modes = ([row[k] for k in where] for row in read.tolist())
     return images, status, modes, slots
 
 
@@ -268,11 +216,7 @@ def decode(files, *, device, dtype=torch.uint8, channels=None, background=None, 
     if resize is not None:
         from . import resize_ops
         resize_ops.filter_id(resample)
-    files = list(files)
-    names = [f"<file {i}>" for i in range(len(files))] if names is None else [os.fspath(n) for n in names]
-    if len(names) != len(files):
-        raise RuntimeError(f"png_decode: {len(files)} files but {len(names)} names")
-    items = [f if isinstance(f, SimpleNamespace) else parse(f, n) for f, n in zip(files, names)]
+    items = decode_stage.parsed("png_decode", files, names, parse)
     kw = dict(device=device, dtype=dtype, channels=channels, background=background, pool=_pool)
     if resize is not None:
         groups(items, channels, background)                                     # (what channels and background ask of the files, before the device)
@@ -320,13 +264,5 @@ def _resized(images, items, size, resample, dtype, channels, background):
 def decode_files(paths, *, device, dtype=torch.uint8, channels=None, background=None, return_modes=False, resize=None, resample="bicubic"):
     """`decode` of files on disk: at most READER_THREADS threads read and parse them and fill the staging buffer."""
     _arguments(device, dtype, background)
-    paths = [os.fspath(p) for p in paths]
-
-    def load(path):
-        with open(path, "rb") as fp:
-            return parse(fp.read(), path)
-
-    with ThreadPoolExecutor(max_workers=max(1, min(READER_THREADS, len(paths)))) as pool:
-        items = list(pool.map(load, paths))
-        return decode(items, device=device, dtype=dtype, channels=channels, background=background, names=paths,
-                      return_modes=return_modes, resize=resize, resample=resample, _pool=pool)
+    return decode_stage.decode_files(paths, parse, decode, device=device, dtype=dtype, channels=channels, background=background,
+                                     return_modes=return_modes, resize=resize, resample=resample)

@@ -242,35 +242,41 @@ def refused(own):
     return out
 
 
-def run_job(exe, d, JD, items, group, dtype, guard, mangle=None, most=None):
+def run_job(exe, d, group, pl, host, dtype, guard, mangle=None, most=None):
     """One process of tests/jpeg_decode_emulate.cpp or tests/jpeg_sync_emulate.cpp (they read the same job file) over one shape group of
-    JD.groups(items) -> the bytes it wrote."""
+    JD.groups(items), pl being its plan of JD.plans and host the array decode_stage.fill wrote -> the bytes it wrote."""
+    import decode_stage_cases as SC
     (H, W, sub), idx = group
-    seg, image_seg, copies, nbytes, top = JD.tables(items, idx)
-    seg = seg if mangle is None else mangle([tuple(r) for r in seg.tolist()])
-    payload = bytearray(nbytes)
-    for at, piece in copies:
-        payload[at:at + len(piece)] = piece
+    seg, image_seg, tables, payload = SC.sections(host, pl)
+    seg = seg if mangle is None else np.array(mangle([tuple(r) for r in pl.seg.tolist()]), dtype=np.int64).tobytes()
     job, out = str(d / "job.bin"), str(d / "out.bin")
     with open(job, "wb") as fp:
-        fp.write(struct.pack("<8iq", len(idx), H, W, sub, 0 if dtype == np.uint8 else 1, len(seg), top if most is None else most, guard, nbytes))
-        fp.write(np.array(seg, dtype=np.int64).tobytes() + np.array(image_seg, dtype=np.int32).tobytes() + b"".join(items[i].tables for i in idx)
-                 + bytes(payload))
+        fp.write(struct.pack("<8iq", len(idx), H, W, sub, 0 if dtype == np.uint8 else 1, len(seg) // 40, pl.most if most is None else most, guard, pl.bytes))
+        fp.write(seg + image_seg + tables + payload)
     subprocess.check_call([exe, job, out], timeout=300)          # (a loop that does not end is a failure here, not a hang)
     return open(out, "rb").read()
+
+
+def staged_groups(items):
+    """[(group, plan)] of JD.groups(items) and the array all of them are staged in, as the device path stages them."""
+    import decode_stage_cases as SC
+    from gaussianprediction_amd import jpeg_decode as JD
+    shapes = JD.groups(items)
+    plans = JD.plans(items, shapes)
+    return list(zip(shapes, plans)), SC.filled(plans)
 
 
 def build_emulator(d, sanitize):
     """tests/jpeg_decode_emulate.cpp built into directory `d`; returns run(items, dtype, guard, mangle, most) -> (images [3, H, W] numpy,
     status), one process per shape group."""
-    from gaussianprediction_amd import jpeg_decode as JD
     exe = emulate_build.build("jpeg_decode_emulate", d, sanitize)
 
     def run(items, dtype=np.uint8, guard=8, mangle=None, most=None):
         images, status = [None] * len(items), [0] * len(items)
-        for group in JD.groups(items):
+        staged, host = staged_groups(items)
+        for group, pl in staged:
             (H, W, _), idx = group
-            raw = run_job(exe, d, JD, items, group, dtype, guard, mangle, most)
+            raw = run_job(exe, d, group, pl, host, dtype, guard, mangle, most)
             B, n = len(idx), 3 * H * W
             words = np.frombuffer(raw[:4 * B], dtype=np.uint32)
             slots = np.frombuffer(raw[4 * B:], dtype=dtype).reshape(B, n + guard)

@@ -157,14 +157,14 @@ def malformed():
 
 def build_emulator(d, sanitize):
     """tests/jpeg_sync_emulate.cpp built into directory `d`; returns run(items, dtype, guard) -> (images [3, H, W] numpy, status, info)."""
-    from gaussianprediction_amd import jpeg_decode as JD
     exe = emulate_build.build("jpeg_sync_emulate", d, sanitize)
 
     def run(items, dtype=np.uint8, guard=8):
         images, status, info = [None] * len(items), [0] * len(items), [None] * len(items)
-        for group in JD.groups(items):
+        staged, host = D.staged_groups(items)
+        for group, pl in staged:
             (H, W, _), idx = group
-            raw = D.run_job(exe, d, JD, items, group, dtype, guard)
+            raw = D.run_job(exe, d, group, pl, host, dtype, guard)
             B, n = len(idx), 3 * H * W
             words = np.frombuffer(raw[:4 * B], dtype=np.uint32)
             infos = np.frombuffer(raw[4 * B:20 * B], dtype=np.uint32).reshape(B, 4)

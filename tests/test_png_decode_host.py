@@ -14,6 +14,7 @@ import pytest
 import torch
 
 import abi_check
+import decode_stage_cases as SC
 import emulate_build
 import png_cases as P
 import png_decode_cases as D
@@ -126,17 +127,17 @@ def emulator(tmp_path_factory):
 
     def run(items, banded, dtype=np.uint8, channels=None, bg=None, guard=8, mangle=None):
         images, status, modes = [None] * len(items), [0] * len(items), [0] * len(items)
-        for (H, W, Cn), c_out, idx in PD.groups(items, channels, None if bg is None else torch.tensor(bg)):
-            seg, image_seg, copies, nbytes = PD.tables(items, banded, idx)
-            seg = seg if mangle is None else mangle(list(seg))
-            payload = bytearray(nbytes)
-            for at, piece in copies:
-                payload[at:at + len(piece)] = piece
+        shapes = PD.groups(items, channels, None if bg is None else torch.tensor(bg))
+        plans = PD.plans(items, banded, shapes)
+        host = SC.filled(plans)                                              # (staged as the device path stages: all groups in one array)
+        for ((H, W, Cn), c_out, idx), pl in zip(shapes, plans):
+            seg, image_seg, _, payload = SC.sections(host, pl)
+            seg = seg if mangle is None else np.array(mangle(list(pl.seg)), dtype=np.int64).tobytes()
             job, out = str(d / "job.bin"), str(d / "out.bin")
             with open(job, "wb") as fp:
-                fp.write(struct.pack("<9i3fq", len(idx), H, W, Cn, c_out, 0 if dtype == np.uint8 else 1, bg is not None, len(seg), guard,
-                                     *(bg if bg is not None else (0, 0, 0)), nbytes))
-                fp.write(np.array(seg, dtype=np.int64).tobytes() + np.array(image_seg, dtype=np.int32).tobytes() + bytes(payload))
+                fp.write(struct.pack("<9i3fq", len(idx), H, W, Cn, c_out, 0 if dtype == np.uint8 else 1, bg is not None, len(seg) // 40, guard,
+                                     *(bg if bg is not None else (0, 0, 0)), pl.bytes))
+                fp.write(seg + image_seg + payload)
             subprocess.check_call([exe, job, out], timeout=120)          # (a loop that does not end is a failure here, not a hang)
             raw = open(out, "rb").read()
             B, n = len(idx), c_out * H * W
