@@ -79,6 +79,10 @@ class GaussianModel(TrainingMixin, nn.Module):
         self.active_sh_degree = degree            # (oneupSHdegree raises it, train.py:81-83; eval.py:241 / train.py:52 set the maximum beforehand)
         return self
 
+    def save_ply(self, path):                      # [REF scene/gaussian_model.py:507-524] (what Scene.save calls)
+        from .io_formats import save_ply
+        save_ply(self, path)
+
     # ---- construction from raw tensors ---------------------------------------------------------
     def create_from_tensors(self, xyz, features_dc, features_rest, scaling, rotation, opacity, motion_feature,
                             keypoints=None, keypoint_features=None, with_weights_model=False):
