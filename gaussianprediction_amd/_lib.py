@@ -230,12 +230,15 @@ ABIS = []                  # every Abi, in import order; the main one (include/g
 class Abi:
     """One header of include/ and its binding: the header's file name, the name of its *_abi_version function, the version this
     binding is written against, and {name: (restype, argtypes)} as the header declares them (tests/abi_check.py compares the two).
-    Constructing one registers it in ABIS; lib() applies the table to the one CDLL handle and checks the version, once."""
+    Constructing one registers it in ABIS; lib() applies the table to the one CDLL handle and checks the version, once.
+    register=False: the same binding and version check without joining ABIS, for a header that is not (yet) one of include/ --
+    `header` is then its path relative to include/."""
 
-    def __init__(self, header, version_fn, version, prototypes):
+    def __init__(self, header, version_fn, version, prototypes, register=True):
         self.header, self.version_fn, self.version, self.prototypes = header, version_fn, version, prototypes
         self._handle = None
-        ABIS.append(self)
+        if register:
+            ABIS.append(self)
 
     def bind(self, l):
         rebuild = "rebuild the library (__graft_entry__.build(force=True))"

@@ -11,7 +11,11 @@ The reference muxes the video frames into an mp4 with cv2 [REF eval.py:113-115];
 render_video stops at the numbered frames in renders_video/ and returns their count, and with `video=` it writes the reference's
 file name with another container beside that directory: ours_<iteration>/<scene>.avi, Motion-JPEG from jpeg_ops.VideoWriter.  The
 files: eval/<name>/ours_<iteration>/{renders, gt}/%05d.png, renders/view_%03d/%05d.png, renders_video/%05d.png -- the trees
-`metrics.evaluate_dirs` scores."""
+`metrics.evaluate_dirs` scores.
+
+  [REF eval.py:38-73]      project_trajectory, drawn on the device (trajectory_ops: this project's own line definition, parity with
+                           cv2.line is unpinned); keypoint_trails for ready-made paths; render_trajectories writes
+                           trajectories/%05d.png and is opt-in -- none of the loops above calls it."""
 from __future__ import annotations
 
 import os
@@ -206,3 +210,80 @@ def render_video(model_path, name, iteration, views, gaussians, pipeline, backgr
     stats = _run(frames(), gaussians, pipeline, background, iteration, writer, renderer, video=VideoWriter(video_path, fps))
     stats["video"] = video_path
     return eval_path, stats
+
+
+# ---- motion trajectories [REF eval.py:38-73] ----------------------------------------------------------------------------------
+def _on_device(what, t):
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise RuntimeError(f"{what} is on {t.device if torch.is_tensor(t) else 'the host'} -- HIP kernels only (no CPU fallback)")
+
+
+def project_trajectory(gaussians, view, tidx, time_freq, iteration, steps=60, colors=None, seed=0, base=None, min_depth=None):
+    """The picture of [REF eval.py:38-73]: for the Gaussian seen at every pixel of `view` (tidx [H, W] int32 from render(), -1 where
+    there is none), the polyline of its projected position at `steps` times from 0 to the view's time, a later line over an earlier
+    one.  Returns [H, W, 3] float32 on the device, over zero or over `base` [3, H, W].  The points are the valid entries of
+    tidx.view(-1) in pixel order; colors: [P, 3] for them, default trajectory_ops.default_colors(P, seed).  The drawing's definition is
+    trajectory_ops' (parity with cv2.line is unpinned).
+
+    Each raw time goes to gaussians.forward(t, iteration) as render() passes it and the step's positions are the model's _last_xyz_t
+    (the reference reads `all_xyz_motion + xyz`, which nothing there assigns).  `time_freq` is accepted for the reference's signature
+    and is unused: the reference encodes the time with it BEFORE forward [REF eval.py:58], and forward encodes its argument again --
+    here forward takes the raw time and encodes it once, with the model's own frequency count.  One read of the device before the
+    loop (the number of valid pixels); none inside it."""
+    from .trajectory_ops import TrajectoryCanvas
+    steps = int(steps)
+    if steps < 1:
+        raise RuntimeError(f"project_trajectory: steps = {steps} must be >= 1")
+    _on_device("project_trajectory: tidx", tidx)
+    if tidx.dim() != 2 or tidx.dtype != torch.int32:
+        raise RuntimeError(f"project_trajectory: tidx must be [H, W] int32 (got {tuple(tidx.shape)} {tidx.dtype})")
+    H, W = tidx.shape
+    flat = tidx.reshape(-1)
+    idx = flat[flat != -1].contiguous()                      # (the one read: the count of valid pixels sizes the tensor)
+    view = _cam(view)
+    canvas = TrajectoryCanvas(view, idx.numel(), tidx.device, H=H, W=W, colors=colors, seed=seed, min_depth=min_depth)
+    end = float(np.asarray(view.time.detach().cpu() if torch.is_tensor(view.time) else view.time).reshape(-1)[0])
+    times = torch.linspace(0, end, steps).to(tidx.device)
+    if canvas.P > 0 and steps > 1:
+        with torch.no_grad():
+            for i in range(steps):
+                gaussians.forward(times[i:i + 1], iteration)
+                canvas.step(gaussians._last_xyz_t, idx)
+    return canvas.image(base)
+
+
+def keypoint_trails(view, kpts_xyz, colors=None, base=None, seed=0, min_depth=None, H=None, W=None):
+    """The same drawing for ready-made paths: kpts_xyz [S, K, 3] float32 on the device, such as the positions of
+    motion.keypoint_trajectories or of a GCN rollout (observed and predicted steps concatenated along S).  Returns [H, W, 3] float32;
+    H, W default to the view's."""
+    from .trajectory_ops import TrajectoryCanvas
+    if not torch.is_tensor(kpts_xyz) or kpts_xyz.dim() != 3 or kpts_xyz.shape[2] != 3:
+        raise RuntimeError("keypoint_trails: kpts_xyz must be a [S, K, 3] tensor")
+    _on_device("keypoint_trails: kpts_xyz", kpts_xyz)
+    canvas = TrajectoryCanvas(_cam(view), kpts_xyz.shape[1], kpts_xyz.device, H=H, W=W, colors=colors, seed=seed, min_depth=min_depth)
+    for xyz in kpts_xyz.detach().to(torch.float32):
+        canvas.step(xyz)
+    return canvas.image(base)
+
+
+def render_trajectories(model_path, name, iteration, views, gaussians, pipeline, background, steps=60, overlay=True, writer=None):
+    """Opt-in (no other loop calls it): per view one exact render() for tidx, then project_trajectory -- over the render with
+    overlay=True -- to eval/<name>/ours_<iteration>/trajectories/%05d.png.  writer: a PngWriter of the caller's (it closes it).
+    Returns (eval_path, {"frames", "seconds"})."""
+    from .renderer import render
+    eval_path = os.path.join(model_path, "eval", name)
+    out_path = os.path.join(eval_path, "ours_{}".format(iteration), "trajectories")
+    os.makedirs(out_path, exist_ok=True)
+    import contextlib
+    own = writer is None
+    dev = background.device
+    start = _time.perf_counter()
+    with (PngWriter() if own else contextlib.nullcontext(writer)) as w:      # (its own writer is closed on every way out)
+        for i, view in enumerate(_cam(v) for v in views):
+            with torch.no_grad():
+                out = render(view, gaussians, pipeline, background, time=_time_of(view, dev), it=iteration)
+            image = project_trajectory(gaussians, view, out["tidx"], None, iteration, steps=steps, base=out["render"] if overlay else None)
+            w.submit(image.permute(2, 0, 1), os.path.join(out_path, "{0:05d}.png".format(i)))
+    if not own:
+        torch.cuda.synchronize(dev)                          # (a caller's writer: its files are complete after its close())
+    return eval_path, {"frames": len(views), "seconds": _time.perf_counter() - start}
