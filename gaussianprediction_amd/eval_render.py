@@ -15,7 +15,9 @@ files: eval/<name>/ours_<iteration>/{renders, gt}/%05d.png, renders/view_%03d/%0
 
   [REF eval.py:38-73]      project_trajectory, drawn on the device (trajectory_ops: this project's own line definition, parity with
                            cv2.line is unpinned); keypoint_trails for ready-made paths; render_trajectories writes
-                           trajectories/%05d.png and is opt-in -- none of the loops above calls it."""
+                           trajectories/%05d.png and is opt-in -- none of the loops above calls it.
+  [REF utils/visualizer_utils.py:57-82]   PCA_vis, as rendered pictures: render_features colours every Gaussian by the leading
+                           principal components of its motion feature (feature_vis) and writes features/%05d.png; opt-in as well."""
 from __future__ import annotations
 
 import os
@@ -287,3 +289,33 @@ def render_trajectories(model_path, name, iteration, views, gaussians, pipeline,
     if not own:
         torch.cuda.synchronize(dev)                          # (a caller's writer: its files are complete after its close())
     return eval_path, {"frames": len(views), "seconds": _time.perf_counter() - start}
+
+
+# ---- feature renders [REF utils/visualizer_utils.py:57-82] ------------------------------------------------------------------------
+def render_features(model_path, name, iteration, views, gaussians, pipeline, background, features=None, dim=3, model=None, writer=None):
+    """Opt-in (no other loop calls it): every view rendered with override_color = the PCA colours of `features` [N, D] (default: the
+    model's motion_feature), to eval/<name>/ours_<iteration>/features/%05d.png.  The basis is fitted once (feature_vis.pca_fit with
+    `dim` components, 3 or 5), unless `model`, a feature_vis.PcaModel, gives a frozen one.  writer: a PngWriter of the caller's (it
+    closes it).  Returns (the features directory, the PcaModel)."""
+    from .feature_vis import pca_fit
+    from .renderer import render
+    import contextlib
+    if features is None:
+        features = gaussians.motion_feature
+    _on_device("render_features: features", features)
+    features = features.detach().contiguous()
+    if model is None:
+        model = pca_fit(features, dim)
+    colors = model.colors(features)
+    out_path = os.path.join(model_path, "eval", name, "ours_{}".format(iteration), "features")
+    os.makedirs(out_path, exist_ok=True)
+    own = writer is None
+    dev = background.device
+    with (PngWriter() if own else contextlib.nullcontext(writer)) as w:      # (its own writer is closed on every way out)
+        for i, view in enumerate(_cam(v) for v in views):
+            with torch.no_grad():
+                out = render(view, gaussians, pipeline, background, time=_time_of(view, dev), it=iteration, override_color=colors)
+            w.submit(out["render"], os.path.join(out_path, "{0:05d}.png".format(i)))
+    if not own:
+        torch.cuda.synchronize(dev)                          # (a caller's writer: its files are complete after its close())
+    return out_path, model
