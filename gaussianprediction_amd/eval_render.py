@@ -319,3 +319,39 @@ def render_features(model_path, name, iteration, views, gaussians, pipeline, bac
     if not own:
         torch.cuda.synchronize(dev)                          # (a caller's writer: its files are complete after its close())
     return out_path, model
+
+
+# ---- segment renders [REF utils/visualizer_utils.py:35-44] ------------------------------------------------------------------------
+def render_segments(model_path, name, iteration, views, gaussians, pipeline, background, labels=None, features=None, bandwidth=None, seeds=None,
+                    writer=None):
+    """Opt-in (no other loop calls it): every view rendered with override_color = feature_vis.label_colors(labels), to
+    eval/<name>/ours_<iteration>/segments/%05d.png -- which Gaussians move together, as parts.  labels [N] int64 on the device; by
+    default the mean-shift labels of `features` [N, D] (default: the model's motion_feature): feature_vis.cluster(features, "MeanShift"),
+    or meanshift_ops.mean_shift(features, bandwidth, seeds) when a bandwidth or seeds are given.  writer: a PngWriter of the caller's (it
+    closes it).  Returns (the segments directory, the MeanShiftResult, or None where the labels were given)."""
+    from .feature_vis import label_colors
+    from .meanshift_ops import mean_shift
+    from .renderer import render
+    import contextlib
+    result = None
+    if labels is None:
+        if features is None:
+            features = gaussians.motion_feature
+        _on_device("render_segments: features", features)
+        result = mean_shift(features.detach().contiguous(), bandwidth=bandwidth, seeds=seeds)      # (cluster(features, "MeanShift") is its .labels)
+        labels = result.labels
+    _on_device("render_segments: labels", labels)
+    colors = label_colors(labels)
+    out_path = os.path.join(model_path, "eval", name, "ours_{}".format(iteration), "segments")
+    os.makedirs(out_path, exist_ok=True)
+    own = writer is None
+    dev = background.device
+    with (PngWriter() if own else contextlib.nullcontext(writer)) as w:      # (its own writer is closed on every way out)
+        for i, view in enumerate(_cam(v) for v in views):
+            with torch.no_grad():
+                out = render(view, gaussians, pipeline, background, time=_time_of(view, dev), it=iteration, override_color=colors)
+            w.submit(out["render"], os.path.join(out_path, "{0:05d}.png".format(i)))
+    if not own:
+        torch.cuda.synchronize(dev)                          # (a caller's writer: its files are complete after its close())
+    return out_path, result
+

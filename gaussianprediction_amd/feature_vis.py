@@ -4,6 +4,9 @@ move TOGETHER, shown by the three leading principal components of their motion f
   [REF utils/visualizer_utils.py:57-82]    PCA_vis: sklearn PCA, np.percentile over all of the transformed values, trimesh export
   [REF utils/visualizer_utils.py:46-54]    draw_motion_feature: one component through matplotlib's jet, np.savetxt
   [REF utils/visualizer_utils.py:95-102]   draw_weights: one keypoint's weights through jet, np.savetxt
+  [REF utils/visualizer_utils.py:35-44]    cluster: sklearn KMeans or MeanShift labels -- here kmeans_ops.kmeans (deterministic; sklearn's
+                                           randomly initialised KMeans labelling is unpinned by nature) or meanshift_ops.mean_shift
+                                           (csrc/gp_meanshift.h, pinned against sklearn), and label_colors for the segment renders
 
 The header states the definition in full: float64 mean and covariance summed in a fixed order, cyclic Jacobi in float64, eigenvalues
 descending, each component signed so that its entry of largest magnitude is positive (sklearn 1.7's svd_flip on the components), a
@@ -304,3 +307,38 @@ def draw_weights(weights_xyz, pcd, super_gaussians, idx, directory="visualize"):
     kpt = super_gaussians.detach().cpu().numpy()[..., :3][idx].reshape([1, 3]).repeat(3, axis=0)
     np.savetxt(os.path.join(directory, f"kpts{idx}.txt"), kpt)
     return colors
+
+
+# ---- clusters -------------------------------------------------------------------------------------------------------------------------
+def cluster(features, method="KMeans", k=4):
+    """[REF utils/visualizer_utils.py:35-44] on the device: labels [N] int64 of features [N, D] (float32, on the device, contiguous).
+    "KMeans": kmeans_ops.kmeans(features, k).ids -- deterministic Lloyd iterations from seeded rows, NOT sklearn's randomly initialised
+    KMeans, whose labelling is unpinned by nature.  Anything else, as the reference's `else:`: meanshift_ops.mean_shift(features).labels,
+    sklearn's MeanShift() with its estimated bandwidth, every row a seed (N * N pairs per step: subsample the seeds of a large cloud
+    through meanshift_ops.mean_shift(features, seeds=...))."""
+    features = _device_f32("cluster: features", features, 2)
+    if method == "KMeans":
+        from . import kmeans_ops
+        return kmeans_ops.kmeans(features, k).ids
+    from . import meanshift_ops
+    return meanshift_ops.mean_shift(features).labels
+
+
+def label_palette(count, seed=0):
+    """[count, 3] float32 on the host: the seeded colours of labels 0 .. count - 1 (the first rows do not depend on count)."""
+    return np.random.RandomState(seed).uniform(0.1, 1.0, size=(max(int(count), 1), 3)).astype(np.float32)
+
+
+LABEL_GREY = (0.5, 0.5, 0.5)        # the colour of label -1 (an orphan of mean_shift(cluster_all=False))
+
+
+def label_colors(labels, seed=0):
+    """labels [N] int64 on the device -> [N, 3] float32: row `label` of label_palette(seed), mid-grey for -1.  One read of the largest
+    label sizes the palette; the gather is torch indexing (plumbing, not a hot path)."""
+    if not torch.is_tensor(labels) or not labels.is_cuda:
+        raise RuntimeError(f"label_colors: labels is on {getattr(labels, 'device', 'the host')} -- HIP kernels only (no CPU fallback)")
+    if labels.dim() != 1 or labels.dtype != torch.int64:
+        raise RuntimeError(f"label_colors: labels must be [N] int64 (got {tuple(labels.shape)}, {labels.dtype})")
+    count = int(labels.max()) + 1 if labels.numel() else 1
+    table = torch.from_numpy(np.concatenate([label_palette(count, seed), np.array([LABEL_GREY], np.float32)])).to(labels.device)
+    return table[torch.where(labels < 0, torch.full_like(labels, table.shape[0] - 1), labels)].contiguous()
