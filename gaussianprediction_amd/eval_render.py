@@ -17,7 +17,10 @@ files: eval/<name>/ours_<iteration>/{renders, gt}/%05d.png, renders/view_%03d/%0
                            cv2.line is unpinned); keypoint_trails for ready-made paths; render_trajectories writes
                            trajectories/%05d.png and is opt-in -- none of the loops above calls it.
   [REF utils/visualizer_utils.py:57-82]   PCA_vis, as rendered pictures: render_features colours every Gaussian by the leading
-                           principal components of its motion feature (feature_vis) and writes features/%05d.png; opt-in as well."""
+                           principal components of its motion feature (feature_vis) and writes features/%05d.png; opt-in as well.
+  [REF scene/cameras.py fwd_flow / bwd_flow, never rendered there]   render_flows: the optical flow between neighbouring views, or of
+                           one camera over a time step, rendered through the composite (flow_ops) and written as colour-wheel
+                           pictures to flows/%05d.png, on request as Middlebury .flo files and a video; opt-in as well."""
 from __future__ import annotations
 
 import os
@@ -355,3 +358,53 @@ def render_segments(model_path, name, iteration, views, gaussians, pipeline, bac
         torch.cuda.synchronize(dev)                          # (a caller's writer: its files are complete after its close())
     return out_path, result
 
+
+
+# ---- optical-flow renders (flow_ops) ------------------------------------------------------------------------------------------------
+def render_flows(model_path, name, iteration, views, gaussians, pipeline, background, dt=None, max_flow=None, alpha_min=1e-3, save_flo=False,
+                 writer=None, video=False):
+    """Opt-in (no other loop calls it): the optical flow of every frame as a colour-wheel picture (flow_ops.colorize; pixels without a
+    valid flow are black) to eval/<name>/ours_<iteration>/flows/%05d.png.  dt=None: frame i is the flow from view i at its time to view
+    i + 1 at its time -- scene and camera motion, len(views) - 1 frames; a number: the flow of view i's own camera from its time to its
+    time + dt -- scene motion alone, len(views) frames.  max_flow=None scales every frame by its own largest magnitude; a number gives
+    one scale for the sequence, which a video needs.  save_flo: also %05d.flo beside every picture (one read of the device per frame,
+    only then).  video: True for ours_<iteration>/<basename(dirname(model_path))>_flows.avi, or a path: the pictures also go, in order,
+    into a Motion-JPEG video as render_video's do, and the statistics gain "video".  `background` names the device only: the flow is
+    composited over zero whatever the scene's background is.  Each frame costs flow_ops.render_flow's three deformation passes.
+    writer: a PngWriter of the caller's (it closes it).  Returns (the flows directory, {"frames", "seconds"})."""
+    from .flow_ops import colorize, render_flow, write_flo
+    import contextlib
+    out_path = os.path.join(model_path, "eval", name, "ours_{}".format(iteration), "flows")
+    os.makedirs(out_path, exist_ok=True)
+    dev = background.device
+    views = [_cam(v) for v in views]
+    if dt is None:
+        frames = [(views[i], _time_of(views[i], dev), _time_of(views[i + 1], dev), views[i + 1]) for i in range(len(views) - 1)]
+    else:
+        frames = [(v, _time_of(v, dev), _time_of(v, dev) + float(dt), None) for v in views]
+    vw, video_path = None, None
+    if video is not None and video is not False:
+        from .jpeg_ops import VideoWriter
+        video_path = (os.path.join(os.path.dirname(out_path), os.path.basename(os.path.dirname(model_path)) + "_flows.avi")
+                      if video is True else os.fspath(video))
+        vw = VideoWriter(video_path, 120)                    # (render_video's default rate)
+    own = writer is None
+    start = _time.perf_counter()
+    with contextlib.ExitStack() as stack:                    # (its own writers are closed on every way out)
+        w = stack.enter_context(PngWriter()) if own else writer
+        if vw is not None:
+            stack.enter_context(vw)
+        for i, (view, t0, t1, view1) in enumerate(frames):
+            res = render_flow(view, gaussians, pipeline, iteration, t0, t1, view1=view1, alpha_min=alpha_min)
+            image = colorize(res.flow, res.valid, max_flow)
+            w.submit(image, os.path.join(out_path, "{0:05d}.png".format(i)))
+            if vw is not None:
+                vw.submit([image])
+            if save_flo:
+                write_flo(os.path.join(out_path, "{0:05d}.flo".format(i)), res.flow)
+    if not own:
+        torch.cuda.synchronize(dev)                          # (a caller's writer: its files are complete after its close())
+    stats = {"frames": len(frames), "seconds": _time.perf_counter() - start}
+    if vw is not None:
+        stats["video"] = video_path
+    return out_path, stats
