@@ -20,7 +20,10 @@ files: eval/<name>/ours_<iteration>/{renders, gt}/%05d.png, renders/view_%03d/%0
                            principal components of its motion feature (feature_vis) and writes features/%05d.png; opt-in as well.
   [REF scene/cameras.py fwd_flow / bwd_flow, never rendered there]   render_flows: the optical flow between neighbouring views, or of
                            one camera over a time step, rendered through the composite (flow_ops) and written as colour-wheel
-                           pictures to flows/%05d.png, on request as Middlebury .flo files and a video; opt-in as well."""
+                           pictures to flows/%05d.png, on request as Middlebury .flo files and a video; opt-in as well.
+  [REF eval.py:109 unwraps the render's "depth" and drops it]   render_depths: the depth map of every view (depth_ops) as a colour-mapped
+                           picture to depths/%05d.png, on request normals/%05d.png, PFM files, the visible surface as points/%05d.ply
+                           and a video; opt-in as well."""
 from __future__ import annotations
 
 import os
@@ -405,6 +408,68 @@ def render_flows(model_path, name, iteration, views, gaussians, pipeline, backgr
     if not own:
         torch.cuda.synchronize(dev)                          # (a caller's writer: its files are complete after its close())
     stats = {"frames": len(frames), "seconds": _time.perf_counter() - start}
+    if vw is not None:
+        stats["video"] = video_path
+    return out_path, stats
+
+
+
+# ---- depth renders (depth_ops) ------------------------------------------------------------------------------------------------------
+def render_depths(model_path, name, iteration, views, gaussians, pipeline, background, mode="disparity", near=None, far=None, alpha_min=1e-3,
+                  normals=False, save_pfm=False, save_ply=False, writer=None, video=False):
+    """Opt-in (no other loop calls it): the depth map of every view at its own time as a colour-mapped picture (depth_ops.colorize
+    with feature_vis.jet_lut; pixels without a valid depth are black) to eval/<name>/ours_<iteration>/depths/%05d.png.  mode: "disparity"
+    (1 / depth, the usual picture) or "depth"; near / far: the values of that quantity at the two ends of the colour table, both or
+    neither -- without them every frame is scaled by its own smallest and largest value, so a video wants fixed near / far.
+    normals: also the camera-space normals (depth_ops.normals, n * 0.5 + 0.5) to a sibling normals/%05d.png.  save_pfm: also %05d.pfm
+    beside every depth picture (one read of the device per frame, only then).  save_ply: also the visible surface as world points to
+    points/%05d.ply (io_formats.save_point_cloud_ply), coloured by an ordinary render() of the same view over `background` -- one more
+    render and the reads of the cloud per frame, only then.  video: True for ours_<iteration>/<basename(dirname(model_path))>_depths.avi,
+    or a path: the depth pictures also go, in order, into a Motion-JPEG video as render_video's do, and the statistics gain "video".
+    The depth itself is composited over zero whatever `background` is.  writer: a PngWriter of the caller's (it closes it).
+    Returns (the depths directory, {"frames", "seconds"})."""
+    from . import depth_ops
+    from .renderer import render
+    import contextlib
+    root = os.path.join(model_path, "eval", name, "ours_{}".format(iteration))
+    out_path = os.path.join(root, "depths")
+    os.makedirs(out_path, exist_ok=True)
+    if normals:
+        os.makedirs(os.path.join(root, "normals"), exist_ok=True)
+    dev = background.device
+    views = [_cam(v) for v in views]
+    vw, video_path = None, None
+    if video is not None and video is not False:
+        from .jpeg_ops import VideoWriter
+        video_path = (os.path.join(root, os.path.basename(os.path.dirname(model_path)) + "_depths.avi") if video is True else os.fspath(video))
+        vw = VideoWriter(video_path, 120)                    # (render_video's default rate)
+    own = writer is None
+    start = _time.perf_counter()
+    with contextlib.ExitStack() as stack:                    # (its own writers are closed on every way out)
+        w = stack.enter_context(PngWriter()) if own else writer
+        if vw is not None:
+            stack.enter_context(vw)
+        for i, view in enumerate(views):
+            t = _time_of(view, dev)
+            res = depth_ops.render_depth(view, gaussians, pipeline, iteration, time=t, alpha_min=alpha_min)
+            image = depth_ops.colorize(res.depth, res.valid, mode, near, far)
+            w.submit(image, os.path.join(out_path, "{0:05d}.png".format(i)))
+            if vw is not None:
+                vw.submit([image])
+            if normals:
+                n, nvalid = depth_ops.normals(res.depth, res.valid, view)
+                w.submit(depth_ops.normals_image(n, nvalid), os.path.join(root, "normals", "{0:05d}.png".format(i)))
+            if save_pfm:
+                depth_ops.write_pfm(os.path.join(out_path, "{0:05d}.pfm".format(i)), res.depth)
+            if save_ply:
+                from .io_formats import save_point_cloud_ply
+                with torch.no_grad():
+                    colour = render(view, gaussians, pipeline, background, time=t, it=iteration)["render"]
+                points, colors = depth_ops.unproject(res.depth, res.valid, view, image=colour.detach())
+                save_point_cloud_ply(os.path.join(root, "points", "{0:05d}.ply".format(i)), points.cpu().numpy(), colors.cpu().numpy())
+    if not own:
+        torch.cuda.synchronize(dev)                          # (a caller's writer: its files are complete after its close())
+    stats = {"frames": len(views), "seconds": _time.perf_counter() - start}
     if vw is not None:
         stats["video"] = video_path
     return out_path, stats
