@@ -23,7 +23,9 @@ files: eval/<name>/ours_<iteration>/{renders, gt}/%05d.png, renders/view_%03d/%0
                            pictures to flows/%05d.png, on request as Middlebury .flo files and a video; opt-in as well.
   [REF eval.py:109 unwraps the render's "depth" and drops it]   render_depths: the depth map of every view (depth_ops) as a colour-mapped
                            picture to depths/%05d.png, on request normals/%05d.png, PFM files, the visible surface as points/%05d.ply
-                           and a video; opt-in as well."""
+                           and a video; opt-in as well.
+  [no counterpart in the reference]   render_meshes: the views of every time step fused into a TSDF volume and extracted as one
+                           watertight, coloured triangle mesh (tsdf_ops) to meshes/%05d.ply; opt-in as well."""
 from __future__ import annotations
 
 import os
@@ -472,4 +474,40 @@ def render_depths(model_path, name, iteration, views, gaussians, pipeline, backg
     stats = {"frames": len(views), "seconds": _time.perf_counter() - start}
     if vw is not None:
         stats["video"] = video_path
+    return out_path, stats
+
+
+# ---- mesh sequences (tsdf_ops) ------------------------------------------------------------------------------------------------------
+def render_meshes(model_path, name, iteration, views, gaussians, pipeline, background, times=None, resolution=256, bounds=None,
+                  voxel_size=None, alpha_min=0.5, color=True):
+    """Opt-in (no other loop calls it): one watertight mesh per time step, from the same cameras, to
+    eval/<name>/ours_<iteration>/meshes/%05d.ply (io_formats.save_mesh_ply).  For every time, ALL `views` are rendered at that time
+    -- depth (depth_ops.render_depth) and, with color, an ordinary render over `background` -- fused into one TSDF volume and
+    extracted (tsdf_ops.fuse).  times: default the distinct times of the views, in their order of first appearance.  resolution,
+    bounds, voxel_size, alpha_min: as tsdf_ops.fuse takes them; without bounds every frame takes its own from the Gaussians at its
+    time, so a sequence that is to share one grid wants fixed bounds.  Per frame the device is read for the mesh's two sizes, the
+    bounds' six floats and the mesh itself.  Returns (the meshes directory, {"frames", "seconds", "vertices", "faces"}), the last
+    two as lists with one number per frame."""
+    from . import tsdf_ops
+    from .io_formats import save_mesh_ply
+    root = os.path.join(model_path, "eval", name, "ours_{}".format(iteration))
+    out_path = os.path.join(root, "meshes")
+    os.makedirs(out_path, exist_ok=True)
+    views = [_cam(v) for v in views]
+    if times is None:
+        times = []
+        for v in views:
+            t = float(np.asarray(v.time, dtype=np.float32).reshape(-1)[0])
+            if t not in times:
+                times.append(t)
+    start = _time.perf_counter()
+    stats = {"frames": 0, "seconds": 0.0, "vertices": [], "faces": []}
+    for i, t in enumerate(times):
+        mesh = tsdf_ops.fuse(views, gaussians, pipeline, iteration, time=t, bounds=bounds, voxel_size=voxel_size, resolution=resolution,
+                             alpha_min=alpha_min, background=background, color=color)
+        save_mesh_ply(os.path.join(out_path, "{0:05d}.ply".format(i)), mesh.vertices, mesh.faces, mesh.colors)
+        stats["frames"] += 1
+        stats["vertices"].append(int(mesh.vertices.shape[0]))
+        stats["faces"].append(int(mesh.faces.shape[0]))
+    stats["seconds"] = _time.perf_counter() - start
     return out_path, stats

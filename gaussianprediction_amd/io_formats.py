@@ -130,6 +130,79 @@ def save_point_cloud_ply(path, points, colors=None, normals=None):
         f.write(table.tobytes())
 
 
+def save_mesh_ply(path, vertices, faces, colors=None):
+    """A triangle mesh as a binary little-endian PLY: the `vertex` element with float x y z and, where there are colours, uchar red
+    green blue = color_to_uint8(colors); the `face` element with `property list uchar int vertex_indices`, three indices each.
+    vertices / colors: [Nv, 3]; faces: [Nf, 3] integers (arrays or tensors anywhere; a device tensor is read once)."""
+    host = lambda a: a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)      # noqa: E731
+    vertices, faces = host(vertices).astype("<f4").reshape(-1, 3), host(faces).astype("<i4").reshape(-1, 3)
+    cols = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")] + ([("red", "u1"), ("green", "u1"), ("blue", "u1")] if colors is not None else [])
+    table = np.empty(vertices.shape[0], dtype=np.dtype(cols))
+    for k, name in enumerate("xyz"):
+        table[name] = vertices[:, k]
+    if colors is not None:
+        colors = color_to_uint8(host(colors)).reshape(-1, 3)
+        if colors.shape != vertices.shape:
+            raise ValueError(f"save_mesh_ply: the colours are {colors.shape}, the vertices {vertices.shape}")
+        for k, name in enumerate(("red", "green", "blue")):
+            table[name] = colors[:, k]
+    if faces.size and (faces.min() < 0 or faces.max() >= vertices.shape[0]):
+        raise ValueError(f"save_mesh_ply: a face names a vertex outside 0 .. {vertices.shape[0] - 1}")
+    rows = np.empty(faces.shape[0], dtype=np.dtype([("n", "u1"), ("v", "<i4", (3,))]))
+    rows["n"], rows["v"] = 3, faces
+    kinds = {"<f4": "float", "u1": "uchar"}
+    header = "ply\nformat binary_little_endian 1.0\n" + f"element vertex {table.shape[0]}\n" + \
+        "".join(f"property {kinds[t]} {n}\n" for n, t in cols) + f"element face {rows.shape[0]}\nproperty list uchar int vertex_indices\nend_header\n"
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "wb") as f:
+        f.write(header.encode("ascii"))
+        f.write(table.tobytes())
+        f.write(rows.tobytes())
+
+
+def read_mesh_ply(path):
+    """(vertices [Nv, 3] float32, faces [Nf, 3] int32, colors [Nv, 3] uint8 or None) of a file save_mesh_ply wrote: binary
+    little-endian, scalar vertex properties, then triangles as `list uchar int`.  Anything else is refused."""
+    with open(path, "rb") as f:
+        if f.readline().strip() != b"ply":
+            raise ValueError(f"{path}: not a PLY file")
+        fmt, counts, props, element = None, {}, [], None
+        while True:
+            line = f.readline()
+            if not line:
+                raise ValueError(f"{path}: unterminated PLY header")
+            tok = line.decode("ascii").split()
+            if not tok:
+                continue
+            if tok[0] == "format":
+                fmt = tok[1]
+            elif tok[0] == "element":
+                element = tok[1]
+                counts[element] = int(tok[2])
+            elif tok[0] == "property" and element == "vertex":
+                if tok[1] == "list":
+                    raise ValueError(f"{path}: list properties on the vertex element are not supported")
+                props.append((tok[2], _PLY_TYPES[tok[1]]))
+            elif tok[0] == "property" and element == "face":
+                if tok[1:] != ["list", "uchar", "int", "vertex_indices"]:
+                    raise ValueError(f"{path}: the face property must be `list uchar int vertex_indices`")
+            elif tok[0] == "end_header":
+                break
+        if fmt != "binary_little_endian" or list(counts) != ["vertex", "face"]:
+            raise ValueError(f"{path}: not a binary little-endian PLY of a vertex and a face element")
+        dt, ft = np.dtype(props), np.dtype([("n", "u1"), ("v", "<i4", (3,))])
+        raw = f.read()
+    if len(raw) != counts["vertex"] * dt.itemsize + counts["face"] * ft.itemsize:
+        raise ValueError(f"{path}: {len(raw)} bytes of data do not hold {counts['vertex']} vertices and {counts['face']} triangles")
+    table = np.frombuffer(raw, dtype=dt, count=counts["vertex"])
+    rows = np.frombuffer(raw, dtype=ft, count=counts["face"], offset=counts["vertex"] * dt.itemsize)
+    if (rows["n"] != 3).any():
+        raise ValueError(f"{path}: a face that is not a triangle")
+    vertices = np.stack([table["x"], table["y"], table["z"]], axis=1).astype(np.float32).reshape(-1, 3)
+    colors = np.stack([table["red"], table["green"], table["blue"]], axis=1).reshape(-1, 3) if "red" in table.dtype.names else None
+    return vertices, np.ascontiguousarray(rows["v"], dtype=np.int32).reshape(-1, 3), colors
+
+
 def load_ply(path, sh_degree=3, device="cpu"):
     """Raw parameter tensors from a reference-format point_cloud.ply (inverse of save_ply)."""
     v = read_ply_vertices(path)
