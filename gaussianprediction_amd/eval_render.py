@@ -479,7 +479,7 @@ def render_depths(model_path, name, iteration, views, gaussians, pipeline, backg
 
 # ---- mesh sequences (tsdf_ops) ------------------------------------------------------------------------------------------------------
 def render_meshes(model_path, name, iteration, views, gaussians, pipeline, background, times=None, resolution=256, bounds=None,
-                  voxel_size=None, alpha_min=0.5, color=True):
+                  voxel_size=None, alpha_min=0.5, color=True, min_triangles=None, keep_largest=None, normals=False):
     """Opt-in (no other loop calls it): one watertight mesh per time step, from the same cameras, to
     eval/<name>/ours_<iteration>/meshes/%05d.ply (io_formats.save_mesh_ply).  For every time, ALL `views` are rendered at that time
     -- depth (depth_ops.render_depth) and, with color, an ordinary render over `background` -- fused into one TSDF volume and
@@ -487,9 +487,13 @@ def render_meshes(model_path, name, iteration, views, gaussians, pipeline, backg
     bounds, voxel_size, alpha_min: as tsdf_ops.fuse takes them; without bounds every frame takes its own from the Gaussians at its
     time, so a sequence that is to share one grid wants fixed bounds.  Per frame the device is read for the mesh's two sizes, the
     bounds' six floats and the mesh itself.  Returns (the meshes directory, {"frames", "seconds", "vertices", "faces"}), the last
-    two as lists with one number per frame."""
+    two as lists with one number per frame.  min_triangles, keep_largest, normals: with any of them, every mesh goes through
+    mesh_ops (components, filter_components with the two criteria, vertex_normals of what is left where normals is set -- written as
+    float nx ny nz) before it is written, "vertices" and "faces" count what is written and the dict gains "components", the
+    components of every frame's mesh before the filter; with all three off the files are byte for byte what they were."""
     from . import tsdf_ops
-    from .io_formats import save_mesh_ply
+    from .io_formats import save_mesh_ply, save_mesh_ply_normals
+    cleanup = min_triangles is not None or keep_largest is not None or bool(normals)
     root = os.path.join(model_path, "eval", name, "ours_{}".format(iteration))
     out_path = os.path.join(root, "meshes")
     os.makedirs(out_path, exist_ok=True)
@@ -502,10 +506,20 @@ def render_meshes(model_path, name, iteration, views, gaussians, pipeline, backg
                 times.append(t)
     start = _time.perf_counter()
     stats = {"frames": 0, "seconds": 0.0, "vertices": [], "faces": []}
+    if cleanup:
+        from . import mesh_ops
+        stats["components"] = []
     for i, t in enumerate(times):
         mesh = tsdf_ops.fuse(views, gaussians, pipeline, iteration, time=t, bounds=bounds, voxel_size=voxel_size, resolution=resolution,
                              alpha_min=alpha_min, background=background, color=color)
-        save_mesh_ply(os.path.join(out_path, "{0:05d}.ply".format(i)), mesh.vertices, mesh.faces, mesh.colors)
+        if cleanup:
+            comps = mesh_ops.connected_components(mesh.faces, mesh.vertices.shape[0])
+            mesh = mesh_ops.filter_components(mesh, min_triangles=min_triangles, keep_largest=keep_largest, components=comps).mesh
+            stats["components"].append(int(comps.labels.shape[0]))
+            save_mesh_ply_normals(os.path.join(out_path, "{0:05d}.ply".format(i)), mesh.vertices, mesh.faces,
+                                  mesh_ops.vertex_normals(mesh.vertices, mesh.faces) if normals else None, mesh.colors)
+        else:
+            save_mesh_ply(os.path.join(out_path, "{0:05d}.ply".format(i)), mesh.vertices, mesh.faces, mesh.colors)
         stats["frames"] += 1
         stats["vertices"].append(int(mesh.vertices.shape[0]))
         stats["faces"].append(int(mesh.faces.shape[0]))

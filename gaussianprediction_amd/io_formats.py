@@ -134,12 +134,29 @@ def save_mesh_ply(path, vertices, faces, colors=None):
     """A triangle mesh as a binary little-endian PLY: the `vertex` element with float x y z and, where there are colours, uchar red
     green blue = color_to_uint8(colors); the `face` element with `property list uchar int vertex_indices`, three indices each.
     vertices / colors: [Nv, 3]; faces: [Nf, 3] integers (arrays or tensors anywhere; a device tensor is read once)."""
+    _write_mesh_ply(path, vertices, faces, colors, None)
+
+
+def save_mesh_ply_normals(path, vertices, faces, normals=None, colors=None):
+    """save_mesh_ply with float nx ny nz after x y z (normals: [Nv, 3], as mesh_ops.vertex_normals gives them); normals=None writes
+    the bytes save_mesh_ply writes."""
+    _write_mesh_ply(path, vertices, faces, colors, normals)
+
+
+def _write_mesh_ply(path, vertices, faces, colors, normals):
     host = lambda a: a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)      # noqa: E731
     vertices, faces = host(vertices).astype("<f4").reshape(-1, 3), host(faces).astype("<i4").reshape(-1, 3)
-    cols = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")] + ([("red", "u1"), ("green", "u1"), ("blue", "u1")] if colors is not None else [])
+    cols = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")] + ([("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")] if normals is not None else []) + \
+        ([("red", "u1"), ("green", "u1"), ("blue", "u1")] if colors is not None else [])
     table = np.empty(vertices.shape[0], dtype=np.dtype(cols))
     for k, name in enumerate("xyz"):
         table[name] = vertices[:, k]
+    if normals is not None:
+        normals = host(normals).astype("<f4").reshape(-1, 3)
+        if normals.shape != vertices.shape:
+            raise ValueError(f"save_mesh_ply: the normals are {normals.shape}, the vertices {vertices.shape}")
+        for k, name in enumerate(("nx", "ny", "nz")):
+            table[name] = normals[:, k]
     if colors is not None:
         colors = color_to_uint8(host(colors)).reshape(-1, 3)
         if colors.shape != vertices.shape:
@@ -160,9 +177,10 @@ def save_mesh_ply(path, vertices, faces, colors=None):
         f.write(rows.tobytes())
 
 
-def read_mesh_ply(path):
+def read_mesh_ply(path, normals=False):
     """(vertices [Nv, 3] float32, faces [Nf, 3] int32, colors [Nv, 3] uint8 or None) of a file save_mesh_ply wrote: binary
-    little-endian, scalar vertex properties, then triangles as `list uchar int`.  Anything else is refused."""
+    little-endian, scalar vertex properties, then triangles as `list uchar int`.  Anything else is refused.  normals=True: a fourth
+    item, the file's nx ny nz as [Nv, 3] float32, or None where it has none."""
     with open(path, "rb") as f:
         if f.readline().strip() != b"ply":
             raise ValueError(f"{path}: not a PLY file")
@@ -200,7 +218,11 @@ def read_mesh_ply(path):
         raise ValueError(f"{path}: a face that is not a triangle")
     vertices = np.stack([table["x"], table["y"], table["z"]], axis=1).astype(np.float32).reshape(-1, 3)
     colors = np.stack([table["red"], table["green"], table["blue"]], axis=1).reshape(-1, 3) if "red" in table.dtype.names else None
-    return vertices, np.ascontiguousarray(rows["v"], dtype=np.int32).reshape(-1, 3), colors
+    faces = np.ascontiguousarray(rows["v"], dtype=np.int32).reshape(-1, 3)
+    if not normals:
+        return vertices, faces, colors
+    held = np.stack([table["nx"], table["ny"], table["nz"]], axis=1).astype(np.float32).reshape(-1, 3) if "nx" in table.dtype.names else None
+    return vertices, faces, colors, held
 
 
 def load_ply(path, sh_degree=3, device="cpu"):
