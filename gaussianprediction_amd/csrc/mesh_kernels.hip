@@ -7,7 +7,8 @@
 //                         every atomic and every store of the round
 //   ms_count_kernel       the vertices and faces of every root by integer atomicAdd (one per wave where the labels agree), face_label
 //   ms_tile_sum_kernel, ms_scan_kernel, ms_rank_kernel     the ordered compaction of a byte array: tile sums, ONE workgroup scans the
-//                         tiles, ballot ranks inside a tile (the order of tsdf_kernels.hip)
+//                         tiles, ballot ranks inside a tile (the order of tsdf_kernels.hip); ms_compact launches the three and is
+//                         declared in mesh_compact.h, for mesh_simplify_kernels.hip
 //   ms_table_kernel       the roots' rows at their ranks
 //   ms_count_key_kernel, ms_keep_label_kernel, ms_keep_vertex_kernel, ms_keep_face_kernel, ms_apply_*_kernel, ms_gather_kernel   the filter
 //   ms_face_vector_kernel, ms_incidence_key_kernel, ms_bounds_kernel, ms_normal_kernel   the normals, around gp_radix_sort_pairs
@@ -15,6 +16,7 @@
 // leaves for another crosses a launch boundary.
 #include "gp_common.h"
 
+#include "mesh_compact.h"
 #include "mesh_core.h"
 
 static_assert(MS_BLOCK == 4 * GP_WAVE && MS_CHUNKS == 16, "the tile order of mesh_core.h: four waves, four steps");
@@ -156,7 +158,7 @@ __global__ void __launch_bounds__(MS_BLOCK) ms_rank_kernel(const uint8_t* __rest
     }
 }
 
-static int ms_compact(const uint8_t* keep, uint32_t n, uint32_t* tile_sums, uint32_t* rank, int32_t* total, hipStream_t st) {
+int ms_compact(const uint8_t* keep, uint32_t n, uint32_t* tile_sums, uint32_t* rank, int32_t* total, hipStream_t st) {
     const uint32_t tiles = (uint32_t)ms_tiles(n);
     if (tiles > 0) {
         hipLaunchKernelGGL(ms_tile_sum_kernel, dim3(tiles), dim3(MS_BLOCK), 0, st, keep, n, tile_sums);

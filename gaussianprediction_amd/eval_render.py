@@ -479,7 +479,8 @@ def render_depths(model_path, name, iteration, views, gaussians, pipeline, backg
 
 # ---- mesh sequences (tsdf_ops) ------------------------------------------------------------------------------------------------------
 def render_meshes(model_path, name, iteration, views, gaussians, pipeline, background, times=None, resolution=256, bounds=None,
-                  voxel_size=None, alpha_min=0.5, color=True, min_triangles=None, keep_largest=None, normals=False):
+                  voxel_size=None, alpha_min=0.5, color=True, weld=False, simplify_voxel=None, simplify_contraction="average", min_triangles=None,
+                  keep_largest=None, normals=False):
     """Opt-in (no other loop calls it): one watertight mesh per time step, from the same cameras, to
     eval/<name>/ours_<iteration>/meshes/%05d.ply (io_formats.save_mesh_ply).  For every time, ALL `views` are rendered at that time
     -- depth (depth_ops.render_depth) and, with color, an ordinary render over `background` -- fused into one TSDF volume and
@@ -490,10 +491,16 @@ def render_meshes(model_path, name, iteration, views, gaussians, pipeline, backg
     two as lists with one number per frame.  min_triangles, keep_largest, normals: with any of them, every mesh goes through
     mesh_ops (components, filter_components with the two criteria, vertex_normals of what is left where normals is set -- written as
     float nx ny nz) before it is written, "vertices" and "faces" count what is written and the dict gains "components", the
-    components of every frame's mesh before the filter; with all three off the files are byte for byte what they were."""
+    components of every frame's mesh before the filter; with all three off the files are byte for byte what they were.
+    weld, simplify_voxel, simplify_contraction: with weld set or a simplify_voxel given, every fused mesh goes through
+    mesh_simplify before the cleanup -- weld first (bit-equal vertices merged, collapsed and doubled faces dropped), then simplify
+    on a grid of side simplify_voxel with that contraction; where `bounds` is given the same box is simplify's, so that a sequence
+    shares one grid and simplify reads the device once a frame.  The dict then gains "fused_vertices" and "fused_faces", the
+    sizes before; "vertices" and "faces" count what is written.  With both off the files are byte for byte what they were."""
     from . import tsdf_ops
     from .io_formats import save_mesh_ply, save_mesh_ply_normals
     cleanup = min_triangles is not None or keep_largest is not None or bool(normals)
+    lighter = bool(weld) or simplify_voxel is not None
     root = os.path.join(model_path, "eval", name, "ours_{}".format(iteration))
     out_path = os.path.join(root, "meshes")
     os.makedirs(out_path, exist_ok=True)
@@ -506,12 +513,22 @@ def render_meshes(model_path, name, iteration, views, gaussians, pipeline, backg
                 times.append(t)
     start = _time.perf_counter()
     stats = {"frames": 0, "seconds": 0.0, "vertices": [], "faces": []}
+    if lighter:
+        from . import mesh_simplify
+        stats["fused_vertices"], stats["fused_faces"] = [], []
     if cleanup:
         from . import mesh_ops
         stats["components"] = []
     for i, t in enumerate(times):
         mesh = tsdf_ops.fuse(views, gaussians, pipeline, iteration, time=t, bounds=bounds, voxel_size=voxel_size, resolution=resolution,
                              alpha_min=alpha_min, background=background, color=color)
+        if lighter:
+            stats["fused_vertices"].append(int(mesh.vertices.shape[0]))
+            stats["fused_faces"].append(int(mesh.faces.shape[0]))
+            if weld:
+                mesh = mesh_simplify.weld(mesh).mesh
+            if simplify_voxel is not None:
+                mesh = mesh_simplify.simplify(mesh, simplify_voxel, contraction=simplify_contraction, bounds=bounds).mesh
         if cleanup:
             comps = mesh_ops.connected_components(mesh.faces, mesh.vertices.shape[0])
             mesh = mesh_ops.filter_components(mesh, min_triangles=min_triangles, keep_largest=keep_largest, components=comps).mesh
