@@ -542,3 +542,62 @@ def render_meshes(model_path, name, iteration, views, gaussians, pipeline, backg
         stats["faces"].append(int(mesh.faces.shape[0]))
     stats["seconds"] = _time.perf_counter() - start
     return out_path, stats
+
+
+# ---- mesh pictures (mesh_render) ----------------------------------------------------------------------------------------------------
+def render_mesh_views(model_path, name, iteration, views, gaussians, pipeline, background, meshes=None, mode="shaded", compare=False, writer=None,
+                      video=False, **fuse):
+    """Opt-in (no other loop calls it): the mesh of every view's time, drawn from that view by the triangle rasterizer
+    (mesh_render.render_mesh: mode "shaded", "color", "normals" or "depth"; pixels without a surface are black) to
+    eval/<name>/ours_<iteration>/mesh_views/%05d.png.  meshes: {time: a tsdf_ops.Mesh}, for instance what a cleanup or a
+    simplification left; without it every distinct time is fused once from ALL `views` (tsdf_ops.fuse with the keywords `fuse`:
+    resolution, bounds, voxel_size, alpha_min, ... over `background`) and kept for the views that share it.  compare: also, per view,
+    one depth_ops.render_depth of the Gaussians and mesh_render.agreement of the mesh depth with it -- the standard depth errors over
+    the pixels both cover, the IoU of the two masks -- as one dict per view in the statistics' "agreement" (one read of the device
+    per view, only then).  video: True for ours_<iteration>/<basename(dirname(model_path))>_mesh_views.avi, or a path: the pictures
+    also go, in order, into a Motion-JPEG video as render_video's do, and the statistics gain "video".  writer: a PngWriter of the
+    caller's (it closes it).  Returns (the mesh_views directory, {"frames", "seconds"})."""
+    from . import depth_ops, mesh_render, tsdf_ops
+    import contextlib
+    root = os.path.join(model_path, "eval", name, "ours_{}".format(iteration))
+    out_path = os.path.join(root, "mesh_views")
+    os.makedirs(out_path, exist_ok=True)
+    dev = background.device
+    views = [_cam(v) for v in views]
+    time_key = lambda v: float(np.asarray(v.time, dtype=np.float32).reshape(-1)[0])          # noqa: E731
+    kept = {float(np.float32(t)): m for t, m in meshes.items()} if meshes is not None else {}
+    vw, video_path = None, None
+    if video is not None and video is not False:
+        from .jpeg_ops import VideoWriter
+        video_path = (os.path.join(root, os.path.basename(os.path.dirname(model_path)) + "_mesh_views.avi") if video is True else os.fspath(video))
+        vw = VideoWriter(video_path, 120)                    # (render_video's default rate)
+    own = writer is None
+    rows = []
+    start = _time.perf_counter()
+    with contextlib.ExitStack() as stack:                    # (its own writers are closed on every way out)
+        w = stack.enter_context(PngWriter()) if own else writer
+        if vw is not None:
+            stack.enter_context(vw)
+        for i, view in enumerate(views):
+            t = time_key(view)
+            if t not in kept:
+                if meshes is not None:
+                    raise KeyError(f"render_mesh_views: no mesh for time {t!r} (meshes holds {sorted(kept)})")
+                kept[t] = tsdf_ops.fuse(views, gaussians, pipeline, iteration, time=t, background=background, **fuse)
+            mesh = kept[t]
+            raster = mesh_render.rasterize(mesh, view)
+            image = mesh_render.render_mesh(mesh, view, mode=mode, raster=raster)
+            w.submit(image, os.path.join(out_path, "{0:05d}.png".format(i)))
+            if vw is not None:
+                vw.submit([image])
+            if compare:
+                res = depth_ops.render_depth(view, gaussians, pipeline, iteration, time=_time_of(view, dev))
+                rows.append(mesh_render.agreement(raster, res))
+    if not own:
+        torch.cuda.synchronize(dev)                          # (a caller's writer: its files are complete after its close())
+    stats = {"frames": len(views), "seconds": _time.perf_counter() - start}
+    if compare:
+        stats["agreement"] = rows
+    if vw is not None:
+        stats["video"] = video_path
+    return out_path, stats
