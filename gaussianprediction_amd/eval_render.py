@@ -601,3 +601,29 @@ def render_mesh_views(model_path, name, iteration, views, gaussians, pipeline, b
     if vw is not None:
         stats["video"] = video_path
     return out_path, stats
+
+
+def mesh_motion(meshes, n=100000, thresholds=None, seed=0, device="cuda"):
+    """Opt-in (no other loop calls it): how far the surface moves from one time step to the next.  meshes: the meshes directory a
+    render_meshes call returned (its %05d.ply files, in order), or a sequence of meshes ((vertices, faces, ...) on the device).
+    Returns one geometry_ops.mesh_distance row per consecutive pair -- mesh k as the prediction, mesh k + 1 as the ground truth, n
+    surface samples each, one read of the device per pair -- with its "frames" (k, k + 1), and under "mean" their mean:
+    {"rows": [...], "mean": {...}}."""
+    from . import geometry_ops
+    from .io_formats import read_mesh_ply
+    thresholds = geometry_ops.THRESHOLDS if thresholds is None else thresholds
+    if isinstance(meshes, (str, os.PathLike)):
+        names = sorted(f for f in os.listdir(meshes) if len(f) == 9 and f.endswith(".ply") and f[:5].isdigit())
+        loaded = []
+        for f in names:
+            vertices, faces = read_mesh_ply(os.path.join(meshes, f))[:2]
+            loaded.append((torch.as_tensor(vertices, dtype=torch.float32).to(device), torch.as_tensor(faces, dtype=torch.int32).to(device)))
+        meshes = loaded
+    meshes = list(meshes)
+    rows = []
+    for k in range(len(meshes) - 1):
+        row = geometry_ops.mesh_distance(meshes[k], meshes[k + 1], n=n, seed=seed, thresholds=thresholds)
+        row["frames"] = (k, k + 1)
+        rows.append(row)
+    mean = geometry_ops.mean_row([{key: v for key, v in r.items() if key != "frames"} for r in rows])
+    return {"rows": rows, "mean": mean}
