@@ -603,12 +603,13 @@ def render_mesh_views(model_path, name, iteration, views, gaussians, pipeline, b
     return out_path, stats
 
 
-def mesh_motion(meshes, n=100000, thresholds=None, seed=0, device="cuda"):
+def mesh_motion(meshes, n=100000, thresholds=None, seed=0, device="cuda", surface=False):
     """Opt-in (no other loop calls it): how far the surface moves from one time step to the next.  meshes: the meshes directory a
     render_meshes call returned (its %05d.ply files, in order), or a sequence of meshes ((vertices, faces, ...) on the device).
     Returns one geometry_ops.mesh_distance row per consecutive pair -- mesh k as the prediction, mesh k + 1 as the ground truth, n
     surface samples each, one read of the device per pair -- with its "frames" (k, k + 1), and under "mean" their mean:
-    {"rows": [...], "mean": {...}}."""
+    {"rows": [...], "mean": {...}}.  surface=True: every pair through mesh_distance(..., surface=True), the samples of each mesh
+    against the other mesh's surface."""
     from . import geometry_ops
     from .io_formats import read_mesh_ply
     thresholds = geometry_ops.THRESHOLDS if thresholds is None else thresholds
@@ -622,7 +623,7 @@ def mesh_motion(meshes, n=100000, thresholds=None, seed=0, device="cuda"):
     meshes = list(meshes)
     rows = []
     for k in range(len(meshes) - 1):
-        row = geometry_ops.mesh_distance(meshes[k], meshes[k + 1], n=n, seed=seed, thresholds=thresholds)
+        row = geometry_ops.mesh_distance(meshes[k], meshes[k + 1], n=n, seed=seed, thresholds=thresholds, surface=surface)
         row["frames"] = (k, k + 1)
         rows.append(row)
     mean = geometry_ops.mean_row([{key: v for key, v in r.items() if key != "frames"} for r in rows])

@@ -162,8 +162,8 @@ def interpolate(samples, mesh, attributes):
     """[n, C] float32: the rows of attributes [Nv, C] float32, 1 <= C <= 8, at the samples, through the weights the points were made
     with: ((B - A) * u1 + A) + (C - A) * u2 over the corners of every sample's face."""
     what = "interpolate"
-    if not isinstance(samples, SurfaceSamples):
-        raise RuntimeError(f"{what}: samples must be a SurfaceSamples (of sample_surface)")
+    if not all(torch.is_tensor(getattr(samples, k, None)) for k in ("face", "bary")):
+        raise RuntimeError(f"{what}: samples must be a SurfaceSamples (of sample_surface) or a surface_ops.PointSurface")
     vertices, faces, nv = _mesh(what, mesh)
     dev = faces.device
     attributes = _rows(what, "attributes", attributes, nv, dev)
@@ -269,11 +269,14 @@ def cloud_distance(a, b, thresholds=THRESHOLDS, cell=None):
     return _row(metrics_table(ab.dist2, ba.dist2, t).tolist(), t)          # (the one read)
 
 
-def mesh_distance(mesh_a, mesh_b, n=100000, seed=0, thresholds=THRESHOLDS, cell=None):
+def mesh_distance(mesh_a, mesh_b, n=100000, seed=0, thresholds=THRESHOLDS, cell=None, surface=False):
     """cloud_distance of n surface samples of each mesh (sample_surface with `seed`, and seed + 1 mod 2^64 for mesh_b, so that a mesh against
     itself is not sample against the same sample).  ONE read: the table and the two sampling refusals together; a mesh without area
-    raises after it."""
+    raises after it.  surface=True: surface_ops.surface_distance instead -- the same samples against the other mesh's surface."""
     what = "mesh_distance"
+    if surface:
+        from .surface_ops import surface_distance
+        return surface_distance(mesh_a, mesh_b, n=n, seed=seed, thresholds=thresholds, cell=cell)
     t = _thresholds(what, thresholds)
     sa, sb = sample_surface(mesh_a, n, seed), sample_surface(mesh_b, n, (int(seed) + 1) % 2 ** 64)
     ab = NearestGrid(sb.points, cell).query(sa.points)
@@ -295,7 +298,7 @@ def mean_row(rows):
         return {}
     out = {}
     for k, v in rows[0].items():
-        if k in ("thresholds", "n", "name"):
+        if k in ("thresholds", "n", "name", "surface"):
             out[k] = v
         elif isinstance(v, list):
             out[k] = [sum(r[k][j] for r in rows) / len(rows) for j in range(len(v))]
@@ -305,10 +308,11 @@ def mean_row(rows):
     return out
 
 
-def evaluate_mesh_dirs(pred_dir, gt_dir, n=100000, thresholds=THRESHOLDS, seed=0, device="cuda"):
+def evaluate_mesh_dirs(pred_dir, gt_dir, n=100000, thresholds=THRESHOLDS, seed=0, device="cuda", surface=False):
     """Pairs the %05d.ply files of two folders by name (io_formats.read_mesh_ply), one mesh_distance(pred, gt) per pair: returns
     {"rows": [one dict per pair, with its "name"], "mean": their mean, "pairs": how many} and writes it as mesh_metrics.json beside
-    pred_dir.  A name only one folder has is left out and listed under "unpaired"."""
+    pred_dir.  A name only one folder has is left out and listed under "unpaired".  surface=True: every pair through
+    mesh_distance(..., surface=True)."""
     from .io_formats import read_mesh_ply
     what = "evaluate_mesh_dirs"
     names = [sorted(f for f in os.listdir(d) if re.fullmatch(r"\d{5}\.ply", f)) for d in (pred_dir, gt_dir)]
@@ -322,7 +326,7 @@ def evaluate_mesh_dirs(pred_dir, gt_dir, n=100000, thresholds=THRESHOLDS, seed=0
 
     rows = []
     for f in both:
-        row = mesh_distance(load(os.path.join(pred_dir, f)), load(os.path.join(gt_dir, f)), n=n, seed=seed, thresholds=thresholds)
+        row = mesh_distance(load(os.path.join(pred_dir, f)), load(os.path.join(gt_dir, f)), n=n, seed=seed, thresholds=thresholds, surface=surface)
         row["name"] = f
         rows.append(row)
     out = {"rows": rows, "mean": mean_row(rows), "pairs": len(rows), "unpaired": sorted(set(names[0]) ^ set(names[1]))}
