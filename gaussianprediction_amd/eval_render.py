@@ -28,6 +28,7 @@ files: eval/<name>/ours_<iteration>/{renders, gt}/%05d.png, renders/view_%03d/%0
                            watertight, coloured triangle mesh (tsdf_ops) to meshes/%05d.ply; opt-in as well."""
 from __future__ import annotations
 
+import json
 import os
 import time as _time
 
@@ -479,8 +480,8 @@ def render_depths(model_path, name, iteration, views, gaussians, pipeline, backg
 
 # ---- mesh sequences (tsdf_ops) ------------------------------------------------------------------------------------------------------
 def render_meshes(model_path, name, iteration, views, gaussians, pipeline, background, times=None, resolution=256, bounds=None,
-                  voxel_size=None, alpha_min=0.5, color=True, weld=False, simplify_voxel=None, simplify_contraction="average", min_triangles=None,
-                  keep_largest=None, normals=False):
+                  voxel_size=None, alpha_min=0.5, smooth=0, smooth_method="taubin", smooth_boundary="fixed", topology_report=False, color=True, weld=False,
+                  simplify_voxel=None, simplify_contraction="average", min_triangles=None, keep_largest=None, normals=False):
     """Opt-in (no other loop calls it): one watertight mesh per time step, from the same cameras, to
     eval/<name>/ours_<iteration>/meshes/%05d.ply (io_formats.save_mesh_ply).  For every time, ALL `views` are rendered at that time
     -- depth (depth_ops.render_depth) and, with color, an ordinary render over `background` -- fused into one TSDF volume and
@@ -496,7 +497,14 @@ def render_meshes(model_path, name, iteration, views, gaussians, pipeline, backg
     mesh_simplify before the cleanup -- weld first (bit-equal vertices merged, collapsed and doubled faces dropped), then simplify
     on a grid of side simplify_voxel with that contraction; where `bounds` is given the same box is simplify's, so that a sequence
     shares one grid and simplify reads the device once a frame.  The dict then gains "fused_vertices" and "fused_faces", the
-    sizes before; "vertices" and "faces" count what is written.  With both off the files are byte for byte what they were."""
+    sizes before; "vertices" and "faces" count what is written.  With both off the files are byte for byte what they were.
+    smooth, smooth_method, smooth_boundary: with smooth > 0 every mesh goes through mesh_smooth.smooth (that many iterations of
+    "taubin" or "laplacian", the boundary "fixed" or "free", the colours untouched) after the simplification and the cleanup and
+    before the normals, so that normals=True writes the normals of the smoothed surface.  topology_report: one row per time step --
+    mesh_smooth.edges' stats of the mesh as written: edges, boundary, non-manifold and inconsistent edges, the Euler characteristic,
+    watertight -- goes to mesh_topology.json beside the meshes directory's files and the dict gains "topology".  Either costs one
+    read of the device a frame (the eight counts; both share it).  With smooth=0 and no report the files are byte for byte what
+    they were."""
     from . import tsdf_ops
     from .io_formats import save_mesh_ply, save_mesh_ply_normals
     cleanup = min_triangles is not None or keep_largest is not None or bool(normals)
@@ -519,6 +527,10 @@ def render_meshes(model_path, name, iteration, views, gaussians, pipeline, backg
     if cleanup:
         from . import mesh_ops
         stats["components"] = []
+    if smooth or topology_report:
+        from . import mesh_smooth
+    if topology_report:
+        stats["topology"] = []
     for i, t in enumerate(times):
         mesh = tsdf_ops.fuse(views, gaussians, pipeline, iteration, time=t, bounds=bounds, voxel_size=voxel_size, resolution=resolution,
                              alpha_min=alpha_min, background=background, color=color)
@@ -533,6 +545,13 @@ def render_meshes(model_path, name, iteration, views, gaussians, pipeline, backg
             comps = mesh_ops.connected_components(mesh.faces, mesh.vertices.shape[0])
             mesh = mesh_ops.filter_components(mesh, min_triangles=min_triangles, keep_largest=keep_largest, components=comps).mesh
             stats["components"].append(int(comps.labels.shape[0]))
+        if smooth or topology_report:
+            topology = mesh_smooth.edges(mesh.faces, mesh.vertices.shape[0])
+            if smooth:
+                mesh = mesh_smooth.smooth(mesh, iterations=smooth, method=smooth_method, boundary=smooth_boundary, topology=topology).mesh
+            if topology_report:
+                stats["topology"].append(dict(topology.stats, frame=i, time=float(t)))
+        if cleanup:
             save_mesh_ply_normals(os.path.join(out_path, "{0:05d}.ply".format(i)), mesh.vertices, mesh.faces,
                                   mesh_ops.vertex_normals(mesh.vertices, mesh.faces) if normals else None, mesh.colors)
         else:
@@ -540,6 +559,9 @@ def render_meshes(model_path, name, iteration, views, gaussians, pipeline, backg
         stats["frames"] += 1
         stats["vertices"].append(int(mesh.vertices.shape[0]))
         stats["faces"].append(int(mesh.faces.shape[0]))
+    if topology_report:
+        with open(os.path.join(out_path, "mesh_topology.json"), "w") as fp:
+            json.dump(stats["topology"], fp, indent=1)
     stats["seconds"] = _time.perf_counter() - start
     return out_path, stats
 
