@@ -631,7 +631,8 @@ def mesh_motion(meshes, n=100000, thresholds=None, seed=0, device="cuda", surfac
     Returns one geometry_ops.mesh_distance row per consecutive pair -- mesh k as the prediction, mesh k + 1 as the ground truth, n
     surface samples each, one read of the device per pair -- with its "frames" (k, k + 1), and under "mean" their mean:
     {"rows": [...], "mean": {...}}.  surface=True: every pair through mesh_distance(..., surface=True), the samples of each mesh
-    against the other mesh's surface."""
+    against the other mesh's surface; surface="signed": the signed columns of sdf_ops.signed_surface_distance with them (a positive
+    signed_accuracy: the surface at step k lies outside the one at step k + 1)."""
     from . import geometry_ops
     from .io_formats import read_mesh_ply
     thresholds = geometry_ops.THRESHOLDS if thresholds is None else thresholds

@@ -272,8 +272,14 @@ def cloud_distance(a, b, thresholds=THRESHOLDS, cell=None):
 def mesh_distance(mesh_a, mesh_b, n=100000, seed=0, thresholds=THRESHOLDS, cell=None, surface=False):
     """cloud_distance of n surface samples of each mesh (sample_surface with `seed`, and seed + 1 mod 2^64 for mesh_b, so that a mesh against
     itself is not sample against the same sample).  ONE read: the table and the two sampling refusals together; a mesh without area
-    raises after it.  surface=True: surface_ops.surface_distance instead -- the same samples against the other mesh's surface."""
+    raises after it.  surface=True: surface_ops.surface_distance instead -- the same samples against the other mesh's surface.
+    surface="signed": sdf_ops.signed_surface_distance -- that row, plus the sign of every sample against the other mesh."""
     what = "mesh_distance"
+    if isinstance(surface, str):
+        if surface != "signed":
+            raise RuntimeError(f"{what}: surface must be False, True or \"signed\"")
+        from .sdf_ops import signed_surface_distance
+        return signed_surface_distance(mesh_a, mesh_b, n=n, seed=seed, thresholds=thresholds, cell=cell)
     if surface:
         from .surface_ops import surface_distance
         return surface_distance(mesh_a, mesh_b, n=n, seed=seed, thresholds=thresholds, cell=cell)
@@ -298,8 +304,10 @@ def mean_row(rows):
         return {}
     out = {}
     for k, v in rows[0].items():
-        if k in ("thresholds", "n", "name", "surface"):
+        if k in ("thresholds", "n", "name", "surface", "signed"):
             out[k] = v
+        elif k == "oriented":
+            out[k] = all(r[k] for r in rows)
         elif isinstance(v, list):
             out[k] = [sum(r[k][j] for r in rows) / len(rows) for j in range(len(v))]
         else:
@@ -312,7 +320,8 @@ def evaluate_mesh_dirs(pred_dir, gt_dir, n=100000, thresholds=THRESHOLDS, seed=0
     """Pairs the %05d.ply files of two folders by name (io_formats.read_mesh_ply), one mesh_distance(pred, gt) per pair: returns
     {"rows": [one dict per pair, with its "name"], "mean": their mean, "pairs": how many} and writes it as mesh_metrics.json beside
     pred_dir.  A name only one folder has is left out and listed under "unpaired".  surface=True: every pair through
-    mesh_distance(..., surface=True)."""
+    mesh_distance(..., surface=True); surface="signed": through mesh_distance(..., surface="signed"), the signed columns with them
+    ("oriented" of the mean: every pair is)."""
     from .io_formats import read_mesh_ply
     what = "evaluate_mesh_dirs"
     names = [sorted(f for f in os.listdir(d) if re.fullmatch(r"\d{5}\.ply", f)) for d in (pred_dir, gt_dir)]
